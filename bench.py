@@ -1,6 +1,6 @@
 """Benchmark: ray-surface intersections/s of the 4-mirror AKB wavefront hot path (+ PSF wall time).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -31,13 +31,25 @@ contiguous blocks of whole 8192-ray numpy sum buffers (Shard.split), so the cros
 numpy's to the bit; the exchanges are tiny all-gathers / all-reduces and the pupil before the PSF
 on rank 0.
 
-Prints one JSON line (rank 0). The dominant kernel's roofline uses HIP events on the stream it runs
-on; its PMC-derived fields (HBM traffic, FP64 rate, the VALU-issue roofline) come from the newest
-profiles/*_roofline.json whose source hash matches the trace kernels' sources, else null.
-cpu_baseline times the oracle's C restatement (the "port") on this host on a bounded sample.
-Outside the timed region: one run() with its host wait (single_run_ms); at N = 1 also the
-faithful PSF chain (griddata + plane correction + psf_calc, faithful_psf_chain_ms) and the
-Huygens stage of configs[1] (huygens_pairs_per_s).
+Prints one JSON line (rank 0). A plain run sets up, warms up, times the K steps and prints the
+line: the headline (value, ms_per_step) and what the timed steps' own HIP events give for nothing
+(the dominant kernel's roofline on the stream it runs on; its PMC-derived fields - HBM traffic,
+FP64 rate, the VALU-issue roofline - come from the newest profiles/*_roofline.json whose source
+hash matches the trace kernels' sources, else null).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed - the arrays a caller
+of the pipelined path receives (RayWave.launch_back's rows, FaithfulPupil.finish's maps and PSF) -
+as DIR/<name>.npy in float64 (dump_outputs below). The inputs depend on the arguments alone, so
+two builds run with the same arguments can be compared file for file.
+
+--full adds every measurement that takes runs of its own, all outside the timed region:
+the same W / K form before the clock ramp (ms_per_step_no_ramp), the PSF alone (psf_alone_ms,
+psf_device_ms), one run() with its host wait (single_run_ms), cpu_baseline (the oracle's C
+restatement, the "port", on this host on a bounded sample); at N = 1 also the faithful PSF chain
+(griddata + plane correction + psf_calc, faithful_psf_chain_ms), the stage API (stage_api), the
+Huygens stage of configs[1] (huygens_pairs_per_s) and C4's band owner's tail (rank0_tail); at
+N > 1 one sharded faithful pupil alone. --no-extras / --no-cpu-baseline / --no-ramp-form leave
+parts of --full out.
 """
 import argparse
 import ctypes
@@ -80,14 +92,21 @@ def parse():
                    help="rays per GPU (default: 1e7 on one GPU, C3; 1.25e7 per rank at N > 1, C4's 1e8 at N = 8)")
     p.add_argument("--systems", type=int, default=8,
                    help="distinct systems cycled through the steps (1: the same system every step)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own, outside the timed region: ms_per_step_no_ramp, "
+                        "psf_alone_ms, single_run_ms, faithful_psf_chain_ms, stage_api, huygens_pairs_per_s, "
+                        "rank0_tail, cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float64; rows per ray as a fixed "
+                        "seeded sample, at most 64 MB in all)")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip single_run_ms / faithful_psf_chain_ms / huygens_pairs_per_s")
+                   help="with --full: skip single_run_ms / faithful_psf_chain_ms / huygens_pairs_per_s")
     p.add_argument("--pupil", type=int, default=128)
     p.add_argument("--faithful-steps", type=int, default=10,
                    help="steps of the trace + faithful-PSF loop reported as faithful_step (outside the timed region)")
     p.add_argument("--pad", type=int, default=16)
     p.add_argument("--cpu-seconds", type=float, default=10.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     p.add_argument("--config", choices=("c2", "c3", "c5"), default="c3",
                    help="c3: BASELINE configs[2] (default, the headline); c5: configs[4], the Legendre "
                         "figure-error OPL perturbation on every ray + a 3-wavelength PSF stack; c2: configs[1], "
@@ -123,7 +142,7 @@ def parse():
                    help="add step_log to the line: per timed step, when its main-stream and back-stream work "
                         "completed (ms after the region's start, device events) and its host time / wait")
     p.add_argument("--no-ramp-form", action="store_true",
-                   help="skip the timed steps before the clock ramp (ms_per_step_no_ramp)")
+                   help="with --full: skip the timed steps before the clock ramp (ms_per_step_no_ramp)")
     p.add_argument("--psf-start", choices=("pupil", "pass1"), default="pupil",
                    help="side-stream PSF starts as soon as the previous pupil is ready, beside pass 1 "
                         "(default; measured faster), or after this step's pass 1")
@@ -579,6 +598,58 @@ def stage_api(rw, geom, dev, reps=5):
     return out
 
 
+DUMP_RAYS = 131072  # rays of a dumped per-ray row (13 rows: 13.6 MB)
+DUMP_PSF_BYTES = 40 << 20  # the PSF stack whole up to this (one 2048^2 float64 plane is 32 MiB)
+
+
+def dump_outputs(path, rays, result):
+    """Write the last timed step's outputs as path/<name>.npy, float64, under 64 MB in all.
+    rays: RayWave.launch_back's result (rows per ray: a fixed sample of DUMP_RAYS ray indices,
+    seed 0, sorted; the indices themselves in ray_index.npy); result: FaithfulPupil.finish's dict
+    (the gridded map, its corrected and rotated forms, the parameter block, the axes - whole - and
+    the PSF stack, whole or a seeded sample of DUMP_PSF_BYTES of it), or (opd, psf) of the stand-in
+    pupil. An array with NaNs (a map outside the hull) is written with zeros there and the NaN
+    mask beside it as <name>_nan.npy, so the files compare with plain arithmetic."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    written = {}
+
+    def put(name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        nan = np.isnan(a)
+        if nan.any():
+            np.save(os.path.join(path, name + "_nan.npy"), nan.astype(np.float32))
+            written[name + "_nan"] = nan.size * 4
+            a = np.where(nan, 0.0, a)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = a.nbytes
+
+    n = rays["opl"].shape[-1]
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_RAYS), replace=False))
+    put("ray_index", idx)
+    didx = torch.from_numpy(idx).to(rays["opl"].device)
+    for k in ("last_hit", "dir_out", "opl", "detcenter2", "total2", "dist_err2", "wave2"):
+        v = rays.get(k)
+        if isinstance(v, torch.Tensor) and v.shape[-1] == n:
+            put(k, v.index_select(v.dim() - 1, didx).cpu().numpy())
+    for k, v in result.items():
+        if not isinstance(v, torch.Tensor):
+            continue
+        if v.dtype == torch.int64:  # (the cone solve's change words: ordered double bits, not values)
+            continue
+        a = v.detach().cpu().numpy()
+        if a.nbytes > DUMP_PSF_BYTES:
+            # (the sample and its indices: half the budget each)
+            pick = np.sort(np.random.default_rng(1).choice(a.size, size=DUMP_PSF_BYTES // 16, replace=False))
+            put(k + "_index", pick)
+            a = a.reshape(-1)[pick]
+        put(k, a)
+    total = sum(written.values())
+    assert total <= 64_000_000, f"--dump-outputs wrote {total} bytes"
+    return {"dir": path, "bytes": total, "arrays": sorted(written)}
+
+
 def _lib_hash():
     from akbraytracing_amd import _lib
     return _lib.sources_hash()
@@ -604,6 +675,8 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     args.warmup = max(args.warmup, 3 if args.fuse >= 2 else 1)
+    if not args.full:  # a plain run: the timed steps and the line, nothing that takes runs of its own
+        args.no_extras = args.no_cpu_baseline = args.no_ramp_form = True
     import torch
     from akbraytracing_amd import build as B
     from akbraytracing_amd import dist as AD
@@ -651,7 +724,7 @@ def main():
     # --back-priority -1 lets the HBM-bound back half take CU slots ahead of the FP64-bound pass 1
     # it overlaps; measured a wash (the host resample then lands on the critical path), so off
     back_stream = torch.cuda.Stream(device=dev, priority=args.back_priority)
-    state = {"psf_done": None}
+    state = {"psf_done": None, "result": None}  # result: the newest faithful finish's (--dump-outputs)
     fronts = []  # launched fronts (pass 1 .. tilt parameters) whose back half is still to queue
 
     # the PSF stack is wavelength-sharded: rank r transforms lams[r::world]
@@ -747,7 +820,7 @@ def main():
                 pe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) \
                     if timed and rank == 0 else None
                 t = tickets.pop(0)
-                fp.finish(t, stream=bs, events=ev, psf_events=pe)
+                state["result"] = fp.finish(t, stream=bs, events=ev, psf_events=pe)
                 finished.append(t)
                 if len(finished) > 1024:  # (the error log keeps 8192 runs: check the ones already done)
                     check_finished(False)
@@ -859,10 +932,13 @@ def main():
     if args.ramp_ms > 0:
         torch.cuda.synchronize()
         r0 = time.perf_counter()
-        while True:  # in chunks of 8 steps, every rank going on while any rank's time is short
-            for _ in range(8):
+        # in chunks of 8 steps (whole cycles of the systems, so that the timed steps trace the same
+        # systems however long the ramp takes), every rank going on while any rank's time is short
+        chunk = len(systems) * -(-8 // len(systems))
+        while True:
+            for _ in range(chunk):
                 step(False)
-            ramp_steps += 8
+            ramp_steps += chunk
             torch.cuda.synchronize()
             more = torch.tensor([float((time.perf_counter() - r0) * 1e3 < args.ramp_ms)],
                                 dtype=torch.float64, device=dev)
@@ -912,15 +988,19 @@ def main():
         back(False)
     while tickets:
         t = tickets.pop(0)
-        fp.finish(t, stream=back_stream)
+        state["result"] = fp.finish(t, stream=back_stream)
         finished.append(t)
     torch.cuda.synchronize()
     faithful_checked = None
     if faithful:  # every run's own error words (the reference's raises), read now that nothing waits on them
         check_finished(True)
         faithful_checked = checked["runs"]
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step's results (rank 0's rows at N > 1)
+        res = state["result"] if faithful else dict(opd=state["pupil"][0], psf=psf_out.get("psf"))
+        dumped = dump_outputs(args.dump_outputs, rw.last, res or {})
     psf_alone_ms = psf_device_ms = None
-    if rank == 0:  # the PSF's own wall time, nothing beside it (the last pupil: rw.pupil is collective)
+    if rank == 0 and args.full:  # the PSF's own wall time, nothing beside it (the last pupil: rw.pupil is collective)
         opd, pitch = (fp.post["opd"], None) if faithful else state["pupil"]
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
@@ -1149,6 +1229,9 @@ def main():
         # provenance: sha256 of the kernel sources compiled into the loaded libakb_hip.so (the
         # loader refuses a library whose hash differs from this tree's, akbraytracing_amd/_lib.py)
         "lib_sources_hash": _lib_hash(),
+        # --full: the measurements with runs of their own were made too; --dump-outputs: what was written
+        "full": bool(args.full),
+        "dumped_outputs": dumped,
     }
     if single_ms is not None:
         out["single_run_ms"] = single_ms

@@ -133,12 +133,13 @@ def test_bench_two_ranks_runs_to_the_json_line(gpu, tmp_path):
     env = dict(os.environ, AKB_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--rays", "250000"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--rays", "250000"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
     assert out["n_gpus"] == 2 and out["value"] > 0
+    assert out["full"] and out["single_run_ms"] > 0 and out["faithful_psf_chain_ms"] > 0  # --full's own runs
 
 
 def test_bench_gpus_flag_launches_the_ranks(gpu):
@@ -156,6 +157,40 @@ def test_bench_gpus_flag_launches_the_ranks(gpu):
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["value"] > 0
     assert out["config"]["rays_total"] == 447 * 447  # round(sqrt(2 x 1e5))^2: C4's weak-scaling grid
+
+
+def test_bench_plain_run_dumps_the_last_step(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps, the line's
+    headline fields, none of --full's own measurements, and the last timed step's arrays as float64
+    .npy files under 64 MB - the sampled rows those of the ray indices in ray_index.npy, the PSF
+    finite and whole, the gridded map's NaNs (outside the hull) as zeros with their mask beside it."""
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rays", "1e5", "--steps", "3",
+           "--warmup", "3", "--ramp-ms", "0", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "intersections/s"
+    assert out["value"] == pytest.approx(out["config"]["intersections_per_step"] / (out["ms_per_step"] * 1e-3))
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["full"] is False
+    for k in ("single_run_ms", "cpu_baseline", "stage_api", "huygens_pairs_per_s", "rank0_tail"):
+        assert k not in out, k
+    assert out["ms_per_step_no_ramp"] is None and out["psf_alone_ms"] is None
+    files = sorted(os.listdir(tmp_path / "out"))
+    arrays = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert sorted(arrays) == out["dumped_outputs"]["arrays"]
+    assert all(a.dtype == np.float64 or a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) == out["dumped_outputs"]["bytes"] <= 64_000_000
+    n = 317 * 317  # ceil(sqrt(1e5))^2 rays
+    idx = arrays["ray_index"]
+    assert idx.shape == (n,) and np.array_equal(idx, np.arange(n))  # fewer rays than the sample: all of them
+    for k, rows in (("last_hit", 3), ("dir_out", 3), ("detcenter2", 3), ("opl", 1), ("wave2", 1), ("dist_err2", 1)):
+        assert arrays[k].shape == ((rows, n) if rows > 1 else (n,)) and np.isfinite(arrays[k]).all(), k
+    assert arrays["psf"].shape == (1, 2048, 2048) and np.isfinite(arrays["psf"]).all() and arrays["psf"].max() > 0
+    assert arrays["map"].shape == (128, 128) and arrays["map_nan"].shape == (128, 128)
+    assert not np.isnan(arrays["map"]).any() and 0 < arrays["map_nan"].sum() < 128 * 128
+    assert (arrays["map"][arrays["map_nan"] == 1] == 0).all()
 
 
 def _huygens_field(n, m, seed=3):

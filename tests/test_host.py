@@ -364,6 +364,42 @@ def test_bench_picks_the_newest_profile_that_matches_the_sources(tmp_path, monke
     assert bench._pick_profile([], "a") == ({}, None, False)
 
 
+def test_bench_dump_outputs_samples_and_masks(tmp_path):
+    """bench.py --dump-outputs' writer on host tensors: rows per ray on the fixed seeded sample
+    (the same indices on every call, written as ray_index), small arrays whole, an array over the
+    PSF budget as a seeded sample with its indices, NaNs as zeros beside their mask, integer words
+    and non-tensors left out, everything float64 / float32 and under 64 MB."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_RAYS + 1000
+    rays = dict(opl=torch.arange(n, dtype=torch.float64), last_hit=torch.arange(3 * n, dtype=torch.float64).reshape(3, n),
+                wave2=torch.arange(n, dtype=torch.float64) * 0.5, dist_err2=None, flags=torch.zeros(1, dtype=torch.int32),
+                slot=0)
+    m = torch.arange(128 * 128, dtype=torch.float64).reshape(128, 128)
+    m[0, :5] = float("nan")
+    big = torch.arange(bench.DUMP_PSF_BYTES // 8 + 8, dtype=torch.float64)
+    res = dict(psf=big, map=m, change=torch.zeros(2, dtype=torch.int64), converged=True)
+    info = bench.dump_outputs(str(tmp_path / "a"), rays, res)
+    again = bench.dump_outputs(str(tmp_path / "b"), rays, res)
+    assert info["arrays"] == again["arrays"] == ["last_hit", "map", "map_nan", "opl", "psf", "psf_index", "ray_index",
+                                                 "wave2"]
+    A = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in info["arrays"]}
+    for k in info["arrays"]:
+        assert np.array_equal(A[k], np.load(tmp_path / "b" / (k + ".npy"))), k
+        assert A[k].dtype in (np.float64, np.float32), k
+    assert info["bytes"] == sum(a.nbytes for a in A.values()) <= 64_000_000
+    idx = A["ray_index"].astype(np.int64)
+    assert idx.shape == (bench.DUMP_RAYS,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(A["opl"], idx) and np.array_equal(A["wave2"], idx * 0.5)
+    assert np.array_equal(A["last_hit"], np.stack([idx, idx + n, idx + 2 * n]))
+    pick = A["psf_index"].astype(np.int64)
+    assert pick.size == bench.DUMP_PSF_BYTES // 16 and np.all(np.diff(pick) > 0) and np.array_equal(A["psf"], pick)
+    assert A["map_nan"].sum() == 5 and (A["map_nan"][0, :5] == 1).all() and (A["map"][0, :5] == 0).all()
+    assert np.array_equal(A["map"][1:], m.numpy()[1:])
+
+
 def _ring_order(W, d):
     """ring d of a W x W box clockwise from its top-left vertex (the plain depth order's ring)"""
     s1 = W - 2 * d - 1
