@@ -749,6 +749,8 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
         opl = opl + d;
     }
     post();
+    // only the flags leave a lean ray (chain_tilt refuses picks): nothing of it stays live across post()
+    if (kLean) return;
     const uint32_t off = (uint32_t)t << 3;
     if (kOPL && (kFixed || a.opl)) st_off(a.opl + i0, off, opl);
     if (!kLean && (kFixed || a.last_hit)) {
@@ -1252,8 +1254,8 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_tilt(ChainArgs a, Tilt
     stage_copy(a);
     tilt_load_params(b);
     // the OPD's means and each thread's running extents live in LDS, and its inputs are loaded
-    // for the current segment only (issued ahead of the tilt arithmetic, which hides part of their
-    // latency): nothing of the OPD is live across the mirror loop
+    // for the current segment only (issued ahead of the tilt arithmetic, consumed behind the tilt
+    // stores and the leaf sums): nothing of the OPD is live across the mirror loop
     __shared__ double om[kOPD ? 4 : 1];
     __shared__ double oe[kOPD ? 4 : 1][kOPD ? kBlock : 1];
     if constexpr (kOPD) {
@@ -1270,8 +1272,8 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_tilt(ChainArgs a, Tilt
     const int t = threadIdx.x;
     const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;
     int64_t seg = blockIdx.x;
-    // software pipeline: segment s's table entries and tilt inputs were loaded during segment
-    // s - gridDim's stores, leaf sums and mirror loop
+    // software pipeline: segment s's table entries and tilt inputs were loaded ahead of segment
+    // s - gridDim's stores, leaf sums and OPD arithmetic, into the registers they are read from
     uint32_t iv = 0, ih = 0;
     double th = 0.0, tv = 0.0;
     TiltIn in;
@@ -1291,24 +1293,28 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_tilt(ChainArgs a, Tilt
         const int64_t nxt = n0 + t;
         const uint32_t off = (uint32_t)t << 3;
         double d2[3], tq[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        OpdIn oin;
         if (valid)
             chain_ray_tab<true, false, false, false, true, true>(a, i0, t, iv, ih, th, tv, fl, qv, [&] {
-                OpdIn oin;
                 if constexpr (kOPD) opd_load(o, b.ld, i0, off, oin);
                 tilt_compute(b, in, d2, tq);
-                if constexpr (kOPD) {  // k_opd's arithmetic, in its order
-                    const double oe2 = (oin.t2 - om[3]) * 1e9;
-                    st_off(o.e2 + i0, off, oe2);
-                    st_off(o.wave + i0, off, oe2 - norm3(oin.x - om[0], oin.y - om[1], oin.z - om[2]) * 1e9);
-                    oe[0][t] = fmax(oe[0][t], oin.y);
-                    oe[1][t] = fmax(oe[1][t], -oin.y);
-                    oe[2][t] = fmax(oe[2][t], oin.z);
-                    oe[3][t] = fmax(oe[3][t], -oin.z);
-                }
-                if (nxt < a.n) {
-                    ray_tables(a, nxt, iv, ih, th, tv);
-                    tilt_load_seg(b, n0, off, in);
-                }
+                // every value that reads this segment's `in` is formed above this line, so the
+                // prefetch lands in `in`'s own registers: a use sunk below the loads would send
+                // them to temporaries, and the copy back would wait for the whole prefetch (one
+                // in-order counter) inside this segment
+                asm volatile(""
+                             : "+v"(d2[0]), "+v"(d2[1]), "+v"(d2[2]), "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]),
+                               "+v"(tq[3]), "+v"(tq[4])
+                             :
+                             : "memory");
+                // ahead of every store of the segment (the next loop top waits for nothing younger),
+                // and under no branch: a lane without a next ray reloads an address this workgroup
+                // has already read (the next segment's first ray, or this segment's), so the count of
+                // loads in flight is the same on every path and the waits behind them stay exact
+                const int64_t p0 = n0 < a.n ? n0 : i0;  // wave-uniform
+                const uint32_t poff = nxt < a.n ? off : 0u;
+                ray_tables(a, p0 + (poff >> 3), iv, ih, th, tv);
+                tilt_load_seg(b, p0, poff, in);
             });
         if (valid) {  // detector-2 rows only (detector 1 and the rotated rays are the full mode's)
             double* r = b.det2 + i0;
@@ -1318,6 +1324,20 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_tilt(ChainArgs a, Tilt
             st_off(b.total2 + i0, off, tq[4]);
         }
         leaf_sink_segment<5>(b.sink, L, i0, tq, valid, t);
+        if constexpr (kOPD) {
+            // k_opd's arithmetic, in its order, behind the tilt stores and the leaf sums: the OPD
+            // rows have had the tilt arithmetic, the stores and two barriers to arrive, and their
+            // registers are held only where the ray's are dead
+            if (valid) {
+                const double oe2 = (oin.t2 - om[3]) * 1e9;
+                st_off(o.e2 + i0, off, oe2);
+                st_off(o.wave + i0, off, oe2 - norm3(oin.x - om[0], oin.y - om[1], oin.z - om[2]) * 1e9);
+                oe[0][t] = fmax(oe[0][t], oin.y);
+                oe[1][t] = fmax(oe[1][t], -oin.y);
+                oe[2][t] = fmax(oe[2][t], oin.z);
+                oe[3][t] = fmax(oe[3][t], -oin.z);
+            }
+        }
     }
     if (fl) atomicOr(a.flags, fl);
     if constexpr (kOPD) {
@@ -1392,7 +1412,8 @@ static inline V3In v3in(const double* p, int64_t ld, int64_t inc) { return V3In{
 // the chain kernels at 4 waves per SIMD (the register allocator's floor; pass 2's fixed-output
 // sink: 89 VGPRs and no scratch; 6 waves spilled 8 VGPRs and was no faster, 8 spilled 160 B and
 // was slower), workgroups capped at 8192 (each walks 256-ray segments grid-stride; measured best
-// for both passes); the OPD kernel at 2048 (its extent atomics grow with the grid)
+// for the unfused passes; the fused pass 1 takes kPass1Rounds rounds of resident workgroups,
+// chain_tilt below); the OPD kernel at 2048 (its extent atomics grow with the grid)
 constexpr int kChainWaves = 4;
 constexpr int64_t kChainGridCap = 256 * 32;
 constexpr int64_t kOpdGridCap = 2048;
@@ -2056,6 +2077,23 @@ int akb_trace_chain_samples_f64(const akb_chain_desc* d, void* stream) {
     return AKB_OK;
 }
 
+// the fused pass 1's grid in rounds of resident workgroups (measured at C3 against the 8192 of the
+// other chain kernels: 1 and 2 rounds lose, 3 to 8 win, 4 is best)
+constexpr int kPass1Rounds = 4;
+// workgroups of the fused pass 1 the device holds at once: three a CU (its LDS pad), 0 if the
+// runtime cannot say
+static int pass1_slots() {
+    static const int cached = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+            return cus * 3;
+        (void)hipGetLastError();
+        return 0;
+    }();
+    return cached;
+}
+
 static int chain_tilt(const akb_chain_desc* d, const double* d_params, const double det1_ghij[4],
                       const double det2_ghij[4], const double* dir, const double* pt, const double* opl, int64_t ld,
                       int64_t n, double* dir_rot, double* pt_rot, double* det1, double* det2, double* total1,
@@ -2082,7 +2120,10 @@ static int chain_tilt(const akb_chain_desc* d, const double* d_params, const dou
                         sink);
     if (st != AKB_OK || empty) return st;
     const int64_t nseg = (n + kLeafSeg - 1) / kLeafSeg;
-    const int64_t gcap = kChainGridCap;
+    // kPass1Rounds rounds of resident workgroups (12 or 13 segments each at C3) instead of the other
+    // chain kernels' 8192: a workgroup's first segment is the one the pipeline cannot prefetch
+    const int64_t slots = (int64_t)kPass1Rounds * pass1_slots();
+    const int64_t gcap = slots > 0 && slots < kChainGridCap ? slots : kChainGridCap;
     const unsigned gs = (unsigned)(nseg < gcap ? nseg : gcap);
     hipStream_t s = (hipStream_t)stream;
     const OpdRows no{};
