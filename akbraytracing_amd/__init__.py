@@ -3,7 +3,9 @@
 Modules
   primitives  drop-in mirr_ray_intersection, norm_vector, reflect_ray, normalize_vector,
               plane_ray_intersection, rotate_vectors, rotate_points (one HIP kernel each)
-  trace       fused K-mirror chain kernel (device-resident), staged exact path
+  extended    the same two functions as the reference's option_mpmath branch: mirr_ray_intersection
+              and reflect_ray in double-double arithmetic, that branch's value rules
+  trace       fused K-mirror chain kernel (device-resident, float64 or double-double), staged exact path
   wavefront   the 'ray_wave' hot path of plot_result_debug / KB_debug on the device
   reduce      numpy-exact device sums (np.sum / np.mean / np.nanmean order)
   psf         compute_psf_fft on rocFFT (+ batched multi-wavelength psf_stack)

@@ -20,7 +20,7 @@ c_int = ctypes.c_int
 c_dbl = ctypes.c_double
 c_vp = ctypes.c_void_p
 MAX_MIRRORS = 7
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 FLAG_MISS = 0x1
 FLAG_ZERO_NORMAL = 0x2
@@ -34,6 +34,7 @@ EXPORTS = [
     "akb_stream_create_reserved", "akb_stream_destroy", "akb_reserved_cu_mask",
     "akb_isect_f64", "akb_normal_f64", "akb_reflect_f64", "akb_normalize_f64", "akb_plane_isect_f64",
     "akb_seglen_f64", "akb_rotate_f64", "akb_fill_nan_f64",
+    "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64",
     "akb_trace_chain_f64", "akb_chain_desc_size", "akb_tilt_opd_f64", "akb_tilt_params_f64",
     "akb_tilt_opd_dev_f64", "akb_chain_tilt_f64", "akb_chain_tilt_opd_f64", "akb_trace_chain_samples_f64", "akb_opd_f64", "akb_resample_f64", "akb_plane_sweep_rows_f64",
     "akb_plane_sweep_sink_f64",
@@ -110,6 +111,9 @@ def _declare(L):
         "akb_isect_f64": ([c_vp] + v3 + v3 + [c_int, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_normal_f64": ([c_vp] + v3 + [c_i64, c_vp, c_i64, c_int, c_vp, c_vp], c_int),
         "akb_reflect_f64": (v3 + v3 + [c_i64, c_vp, c_i64, c_int, c_vp, c_vp], c_int),
+        "akb_isect_dd_f64": ([c_vp] + v3 + v3 + [c_int, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
+        "akb_reflect_dd_f64": (v3 + v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
+        "akb_trace_chain_dd_f64": ([ctypes.POINTER(ChainDesc), c_vp], c_int),
         "akb_normalize_f64": (v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_plane_isect_f64": ([c_vp] + v3 + v3 + [c_i64, c_vp, c_i64, c_vp], c_int),
         "akb_seglen_f64": (v3 + v3 + [c_i64, c_vp, c_vp], c_int),

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "akb_common.h"
+#include "akb_dd.h"
 #include "akb_pairwise.h"
 #include "akb_sincos.h"
 
@@ -83,6 +84,40 @@ __global__ void __launch_bounds__(kBlock) k_reflect(V3In dir, V3In nrm, int64_t 
         } else {
             out.store(i, rx, ry, rz);
         }
+    }
+    if (fl) atomicOr(flags, fl);
+}
+
+// The option_mpmath branch's two primitives (akb_dd.h): one ray per lane, the double-double
+// arithmetic in registers, the coefficients wave-uniform from the argument segment. The branch's
+// value rules are per column and applied here: a NaN column where D < 0, a zero-norm reflection left
+// as it is; the flag bits only report that some column took them.
+struct Coef10 {
+    double c[10];
+};
+
+__global__ void __launch_bounds__(kBlock) k_isect_dd(Coef10 Q, V3In dir, V3In org, int negative, int64_t n,
+                                                     V3Out out, int32_t* flags) {
+    int fl = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        double x, y, z;
+        const bool ok = akb_dd::quadric_hit_dd(Q.c, dir.x(i), dir.y(i), dir.z(i), org.x(i), org.y(i), org.z(i),
+                                               negative != 0, x, y, z);
+        if (!ok) fl |= AKB_FLAG_MISS;
+        out.store(i, x, y, z);
+    }
+    if (fl) atomicOr(flags, fl);
+}
+
+__global__ void __launch_bounds__(kBlock) k_reflect_dd(V3In dir, V3In nrm, int64_t n, V3Out out, int32_t* flags) {
+    int fl = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        double rx, ry, rz;
+        const bool ok = akb_dd::reflect_dd(dir.x(i), dir.y(i), dir.z(i), nrm.x(i), nrm.y(i), nrm.z(i), rx, ry, rz);
+        if (!ok) fl |= AKB_FLAG_ZERO_REFLECT;
+        out.store(i, rx, ry, rz);
     }
     if (fl) atomicOr(flags, fl);
 }
@@ -810,6 +845,102 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain(ChainArgs a) {
     const int t = threadIdx.x;
     for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
         if (i0 + t < a.n) chain_ray<kGrid, kOPL, false, kHits, false, kPointSrc>(a, i0, t, fl, qv);
+    if (fl) atomicOr(a.flags, fl);
+}
+
+// The chain as the reference runs it with option_mpmath set: only mirr_ray_intersection and
+// reflect_ray have an mpmath branch, so per mirror the intersection and the reflection run in
+// double-double (akb_dd.h) and are rounded to float64, and everything between and after them - the
+// segment length, norm_vector, the detector plane, the arctan rows - is the stage kernels' float64
+// arithmetic on those rounded values: the outputs are the staged composition's, bit for bit. One
+// ray per lane, the mirror loop not unrolled so each mirror's coefficients stay scalar loads from
+// the argument segment. VALU-bound (a mirror is ~1.5 k FP64 operations); no LDS, no sink.
+__global__ void __launch_bounds__(kBlock) k_chain_dd(ChainArgs a) {
+    int fl = 0;
+    const int t = threadIdx.x;
+    const bool grid = a.dir == nullptr;
+    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = i0 + t;
+        if (i >= a.n) continue;
+        const int64_t g = a.g0 + i;
+        uint32_t iv = 0, ih = 0;
+        double l, m, n;
+        if (grid) {  // k_normalize of (1, tan_h[ih], tan_v[iv])
+            double th, tv;
+            ray_tables(a, i, iv, ih, th, tv);
+            const double s = norm3(1.0, th, tv);
+            if (s == 0.0) fl |= AKB_FLAG_CHAIN_DIR;
+            l = 1.0 / s;
+            m = th / s;
+            n = tv / s;
+        } else {
+            l = a.dir[i * a.dir_inc];
+            m = a.dir[a.dir_ld + i * a.dir_inc];
+            n = a.dir[2 * a.dir_ld + i * a.dir_inc];
+        }
+        double p, q, r;
+        if (a.org) {
+            p = a.org[i * a.org_inc];
+            q = a.org[a.org_ld + i * a.org_inc];
+            r = a.org[2 * a.org_ld + i * a.org_inc];
+        } else {
+            p = a.src[0];
+            q = a.src[1];
+            r = a.src[2];
+        }
+        double opl = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < a.K; ++k) {
+            const CMirror& M = a.q[k];
+            const double Qc[10] = {M.a, M.b, M.c, M.d, M.e, M.f, M.g, M.h, M.i, M.j};
+            double x, y, z;
+            if (!akb_dd::quadric_hit_dd(Qc, l, m, n, p, q, r, M.sgn < 0.0, x, y, z)) fl |= AKB_FLAG_MISS << (4 * k);
+            if (a.opl) opl = opl + norm3(x - p, y - q, z - r);  // k_seglen; 0 + d is d
+            if (a.hits) {
+                double* h = a.hits + (int64_t)k * 3 * a.hits_ld + i;
+                h[0] = x;
+                h[a.hits_ld] = y;
+                h[2 * a.hits_ld] = z;
+            }
+            double nx, ny, nz;  // k_normal
+            quadric_grad(Quadric{M.a, M.b, M.c, M.d, M.e, M.f, M.g, M.h, M.i, M.j}, x, y, z, nx, ny, nz);
+            const double sn = norm3(nx, ny, nz);
+            if (sn == 0.0) fl |= AKB_FLAG_ZERO_NORMAL << (4 * k);
+            nx = nx / sn;
+            ny = ny / sn;
+            nz = nz / sn;
+            double rx, ry, rz;
+            if (!akb_dd::reflect_dd(l, m, n, nx, ny, nz, rx, ry, rz)) fl |= AKB_FLAG_ZERO_REFLECT << (4 * k);
+            l = rx;
+            m = ry;
+            n = rz;
+            p = x;
+            q = y;
+            r = z;
+        }
+        if (a.opl) a.opl[i] = opl;
+        if (a.last_hit) {
+            a.last_hit[i] = p;
+            a.last_hit[a.last_hit_ld + i] = q;
+            a.last_hit[2 * a.last_hit_ld + i] = r;
+        }
+        if (a.dir_out) {
+            a.dir_out[i] = l;
+            a.dir_out[a.dir_out_ld + i] = m;
+            a.dir_out[2 * a.dir_out_ld + i] = n;
+        }
+        if (a.det_out) {
+            double x, y, z;
+            plane_hit(a.det[0], a.det[1], a.det[2], a.det[3], l, m, n, p, q, r, x, y, z);
+            a.det_out[i] = x;
+            a.det_out[a.det_out_ld + i] = y;
+            a.det_out[2 * a.det_out_ld + i] = z;
+        }
+        if (a.atan_h) a.atan_h[i] = atan_slope(m / l);
+        if (a.atan_v) a.atan_v[i] = atan_slope(n / l);
+        if (a.samp_h && g >= a.sh_begin && g < a.sh_end) a.samp_h[g - a.sh_begin] = m / l;
+        if (a.samp_v && grid && ih == a.sv_col) a.samp_v[iv] = n / l;
+    }
     if (fl) atomicOr(a.flags, fl);
 }
 
@@ -1561,6 +1692,38 @@ int akb_reflect_f64(const double* dir, int64_t dir_ld, int64_t dir_inc, const do
     return launch_status("k_reflect");
 }
 
+// the double-double kernels are VALU-bound (~1 k FP64 operations per ray): eight resident waves per
+// SIMD's worth of workgroups covers the device, the rest of a large batch walks grid-stride
+constexpr int64_t kDDGridCap = 256 * 8;
+
+int akb_isect_dd_f64(const double coeffs[10], const double* dir, int64_t dir_ld, int64_t dir_inc,
+                     const double* org, int64_t org_ld, int64_t org_inc, int negative, int64_t n,
+                     double* out, int64_t out_ld, int32_t* flags, void* stream) {
+    clear_error();
+    AKB_REQUIRE(coeffs && dir && org && out && flags, "null pointer");
+    AKB_REQUIRE(n >= 0, "n < 0");
+    AKB_REQUIRE(out_ld >= n, "out_ld < n");
+    if (n == 0) return AKB_OK;
+    Coef10 Q;
+    for (int k = 0; k < 10; ++k) Q.c[k] = coeffs[k];
+    k_isect_dd<<<grid_for(n, 1, kDDGridCap), kBlock, 0, (hipStream_t)stream>>>(
+        Q, v3in(dir, dir_ld, dir_inc), v3in(org, org_ld, org_inc), negative, n, V3Out{out, out_ld}, flags);
+    return launch_status("k_isect_dd");
+}
+
+int akb_reflect_dd_f64(const double* dir, int64_t dir_ld, int64_t dir_inc, const double* nrm,
+                       int64_t nrm_ld, int64_t nrm_inc, int64_t n, double* out, int64_t out_ld,
+                       int32_t* flags, void* stream) {
+    clear_error();
+    AKB_REQUIRE(dir && nrm && out && flags, "null pointer");
+    AKB_REQUIRE(n >= 0, "n < 0");
+    AKB_REQUIRE(out_ld >= n, "out_ld < n");
+    if (n == 0) return AKB_OK;
+    k_reflect_dd<<<grid_for(n, 1, kDDGridCap), kBlock, 0, (hipStream_t)stream>>>(
+        v3in(dir, dir_ld, dir_inc), v3in(nrm, nrm_ld, nrm_inc), n, V3Out{out, out_ld}, flags);
+    return launch_status("k_reflect_dd");
+}
+
 int akb_normalize_f64(const double* v, int64_t v_ld, int64_t v_inc, int64_t n, double* out,
                       int64_t out_ld, int32_t* flags, void* stream) {
     clear_error();
@@ -1770,6 +1933,35 @@ int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
             launch_chain<false, false, false>(w, gsz, s, a);
     }
     return launch_status("k_chain");
+}
+
+int akb_trace_chain_dd_f64(const akb_chain_desc* d, void* stream) {
+    clear_error();
+    ChainArgs a;
+    bool empty;
+    const int st = chain_args_from(d, a, empty);
+    if (st != AKB_OK) return st;
+    // fields this kernel does not implement are refused, never ignored
+    if (d->sink.nq != 0) {
+        set_error("akb_trace_chain_dd_f64: the fused reduction (sink) is not implemented for the double-double chain");
+        return AKB_E_ARG;
+    }
+    if (d->pert_h || d->pert_v || d->pert_terms != 0) {
+        set_error("akb_trace_chain_dd_f64: the OPL perturbation (pert_*) is not implemented for the double-double chain");
+        return AKB_E_ARG;
+    }
+    if (d->copy_n != 0 || d->copy_src || d->copy_dst) {
+        set_error("akb_trace_chain_dd_f64: the staging copy (copy_*) is not implemented for the double-double chain");
+        return AKB_E_ARG;
+    }
+    if (empty) return AKB_OK;
+    if (d->hits) AKB_REQUIRE(d->hits_ld >= d->n_rays, "hits_ld < n_rays");
+    if (d->last_hit) AKB_REQUIRE(d->last_hit_ld >= d->n_rays, "last_hit_ld < n_rays");
+    if (d->dir_out) AKB_REQUIRE(d->dir_out_ld >= d->n_rays, "dir_out_ld < n_rays");
+    if (d->det_out) AKB_REQUIRE(d->det_out_ld >= d->n_rays, "det_out_ld < n_rays");
+    if (d->dir == nullptr) AKB_REQUIRE(d->samp_h == nullptr || d->samp_h_end >= d->samp_h_begin, "bad samp_h range");
+    k_chain_dd<<<grid_for(d->n_rays, 1, kDDGridCap), kBlock, 0, (hipStream_t)stream>>>(a);
+    return launch_status("k_chain_dd");
 }
 
 // Kernel arguments of a batched launch travel through pinned host memory: a small ring of slots,

@@ -39,7 +39,7 @@ def ray_wave_conditions(option_HighNA=True):
 
 def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), option_set=True, option_HighNA=True,
                          option_energy="EUV", option_AKB=True, directory=None, workdir=None, verbose=True,
-                         as_dict=False, option_legendre=True):
+                         as_dict=False, option_legendre=True, option_mpmath=False):
     """The 'ray_wave' mode with option_save=True for the AKB system built from params on a
     ray_num x ray_num grid. With option_legendre (the alignment loops' call) returns
     (inner_products, orders, pvs) as the reference (:3775); without it (the plotting run) writes the
@@ -47,13 +47,20 @@ def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), optio
     (:3913) - its figures are not drawn. np.inf where the reference returns np.inf (an unbuildable
     system). directory: the module's directory_name (psf_calc's and the txt / csv outputs);
     workdir: where the reference's cwd-relative 'matrixWave2(nm).txt' goes (default: the current
-    directory). as_dict: also return the intermediate maps (device tensors)."""
+    directory). as_dict: also return the intermediate maps (device tensors).
+    option_mpmath: the reference's flag of that name (:92) - the system is built with the
+    double-double intersection and reflection (extended.prims) and traced by
+    RayWave(precision="dd"); everything downstream is unchanged."""
     from . import geometry as G
     from .affine import extract_affine_square_region
     from .psfcalc import psf_calc
     from .pupilmap import match_legendre_multi, wave_maps
     from .wavefront import RayWave, SystemGeometry
-    b = G.build_akb(params, source_shift=source_shift, option_set=option_set)
+    if option_mpmath:
+        from .extended import prims
+        b = G.build_akb(params, source_shift=source_shift, option_set=option_set, prims=prims)
+    else:
+        b = G.build_akb(params, source_shift=source_shift, option_set=option_set)
     if not isinstance(b, dict):
         return b
     defocus_wave, lambda_ = ray_wave_conditions(option_HighNA)
@@ -62,7 +69,10 @@ def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), optio
     det2[9] = -(np.float64(b["s2f_middle"]) + np.float64(b["defocus"]) + defocus_wave)  # coeffs_det2, :3618-3620
     b = dict(b, det2=[float(x) for x in det2], defocus_wave_m=defocus_wave)
     n = int(ray_num)
-    run = RayWave(SystemGeometry.from_dict(b), n).run()
+    if option_mpmath:
+        run = RayWave(SystemGeometry.from_dict(b), n, precision="dd").run()
+    else:
+        run = RayWave(SystemGeometry.from_dict(b), n).run()
     m = wave_maps(run["detcenter2"], run["dist_err2"], run["wave2"], n, n)
     matrixWave2 = m["matrixWave2"].cpu().numpy()
     workdir = os.getcwd() if workdir is None else workdir

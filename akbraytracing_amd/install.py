@@ -27,6 +27,11 @@ install(mod, names=[...]) picks a subset; uninstall(mod) restores every original
 
 The wrappers read the module's live `option_mpmath` flag (AKB_raytrace_20250312.py:92) at call
 time and hand the call to the original function when it is set (the mpmath branch, :399-443).
+install(mod, mpmath="device") keeps the flag's meaning but runs it on the device instead: the two
+functions with an mpmath branch call extended.py's double-double kernels while the flag is set, and
+plot_result_debug's 'ray_wave' mode runs driver.plot_result_ray_wave(option_mpmath=True) (the
+alignment scripts set the flag around exactly that call, :13853-14043). Every other mode still runs
+the reference's function under the flag, on the rebound primitives.
 """
 from . import primitives as _P
 from . import psf as _psf
@@ -50,11 +55,14 @@ def _psf_calc_for(mod):
         return None  # the reference's psf_calc returns nothing; its results are the .npy files
     return psf_calc
 
+def _akb_system_ok(mod):
+    return getattr(mod, "option_AKB", False) and getattr(mod, "option_wolter_3_1", False)
+
+
 def _akb_native_ok(mod):
     """The batched focus search restates the Wolter III+I system of the live plot_result_debug
     (:1325 `if option_wolter_3_1`) for option_AKB; anything else stays the reference's."""
-    return (getattr(mod, "option_AKB", False) and getattr(mod, "option_wolter_3_1", False)
-            and not getattr(mod, "option_mpmath", False))
+    return _akb_system_ok(mod) and not getattr(mod, "option_mpmath", False)
 
 
 def _kb_native_ok(mod):
@@ -101,12 +109,13 @@ def _kb_debug_for(mod, original):
     return KB_debug
 
 
-def _plot_result_debug_for(mod, original):
+def _plot_result_debug_for(mod, original, mpmath="reference"):
     """plot_result_debug with its 'test' mode (the one auto_focus_NA and the alignment loops call
     hundreds of times), its 'sep' mode (auto_focus_sep's, sep.py), its 'wave' mode and its 'ray_wave'
     mode (driver.py: with option_legendre the alignment loops' call, without it the plotting run -
     the same device chain and files, its figures not drawn) on the device; every other mode runs the
-    reference's own function, whose primitives install() has rebound."""
+    reference's own function, whose primitives install() has rebound. mpmath="device": 'ray_wave'
+    also runs on the device while option_mpmath is set, through the double-double chain."""
     def plot_result_debug(params, option, source_shift=[0., 0., 0.], option_tilt=True, option_legendre=False,
                           angular_shift=[0., 0.], option_save=True):
         if option == "test" and _akb_native_ok(mod) and list(angular_shift) == [0., 0.]:
@@ -116,7 +125,9 @@ def _plot_result_debug_for(mod, original):
             from .sep import plot_result_sep
             return plot_result_sep(params, source_shift, option_tilt, option_set=bool(getattr(mod, "option_set", False)),
                                    widesearch=bool(getattr(mod, "widesearch", False)))
-        if (option == "ray_wave" and option_save and option_tilt and _akb_native_ok(mod)
+        use_dd = mpmath == "device" and bool(getattr(mod, "option_mpmath", False))
+        rw_ok = _akb_system_ok(mod) if use_dd else _akb_native_ok(mod)
+        if (option == "ray_wave" and option_save and option_tilt and rw_ok
                 and list(angular_shift) == [0., 0.] and getattr(mod, "wave_num_H", 0) == getattr(mod, "wave_num_V", 1)):
             # the whole chain on the device (driver.py): the alignment loops' call (option_legendre)
             # and the live __main__ plotting run (:14603-14611; its figures not drawn)
@@ -126,7 +137,7 @@ def _plot_result_debug_for(mod, original):
                                         option_HighNA=getattr(mod, "option_HighNA", True),
                                         option_energy=getattr(mod, "option_energy", "EUV"), option_AKB=True,
                                         directory=getattr(mod, "directory_name", None),
-                                        option_legendre=bool(option_legendre))
+                                        option_legendre=bool(option_legendre), option_mpmath=use_dd)
         if (option == "wave" and _akb_native_ok(mod) and list(angular_shift) == [0., 0.]
                 and getattr(mod, "option_rotate", True) and getattr(mod, "wave_num_H", 0) == getattr(mod, "wave_num_V", 1)):
             from .wavedata import plot_result_wave
@@ -223,42 +234,60 @@ NATIVE_NAMES = tuple(_NATIVE)
 _MPMATH_AWARE = {"mirr_ray_intersection", "reflect_ray"}
 
 
-def _wrap(mod, name, original, native):
+def _wrap(mod, name, original, native, mpmath="reference"):
+    extended = _lazy("extended", name) if (name in _MPMATH_AWARE and mpmath == "device") else None
+
     def wrapper(*args, **kwargs):
         if name in _MPMATH_AWARE and getattr(mod, "option_mpmath", False):
+            if extended is not None:
+                return extended(*args, **kwargs)
             return original(*args, **kwargs)
         return native(*args, **kwargs)
     wrapper.__name__ = name
     wrapper.__wrapped__ = original
     wrapper.__akb_native__ = True
+    wrapper.__akb_mpmath__ = mpmath
     return wrapper
 
 
-def install(mod, names=None):
+def install(mod, names=None, mpmath="reference"):
     """Rebind `names` (default: every hot-path name the module defines, NATIVE_NAMES) in `mod`.
     Returns the list of rebound names. uninstall(mod) restores the originals.
+
+    mpmath: what the module's live option_mpmath flag selects while it is set - "reference" (the
+    default): the reference's own mpmath loops and, for 'ray_wave', its own driver; "device":
+    extended.py's double-double kernels and driver.plot_result_ray_wave(option_mpmath=True). A name
+    installed before with the other setting is rebound.
 
     Parity unpinned: extract_affine_square_region (AKB_raytrace_20250312.py:1047-1119) restates
     OpenCV's findContours / approxPolyDP / warpAffine; cv2 is not importable here and the reference
     holds no recorded output of it, so it is checked only against oracle/affine.py and closed forms.
     Leave it out of `names` to keep the reference's cv2 step."""
+    if mpmath not in ("reference", "device"):
+        raise ValueError('mpmath must be "reference" or "device"')
     done = []
     for name in (names or _NATIVE):
         if name not in _NATIVE or not hasattr(mod, name):
             continue
         cur = getattr(mod, name)
         if getattr(cur, "__akb_native__", False):
-            done.append(name)
-            continue
+            if getattr(cur, "__akb_mpmath__", mpmath) == mpmath:
+                done.append(name)
+                continue
+            cur = cur.__wrapped__
         if name in _PER_MODULE:
-            w = _PER_MODULE[name](mod, cur)
+            if name == "plot_result_debug":
+                w = _plot_result_debug_for(mod, cur, mpmath)
+                w.__akb_mpmath__ = mpmath
+            else:
+                w = _PER_MODULE[name](mod, cur)
             w.__wrapped__ = cur
             w.__akb_native__ = True
             setattr(mod, name, w)
             done.append(name)
             continue
         native = _NATIVE[name] if _NATIVE[name] is not None else _psf_calc_for(mod)
-        setattr(mod, name, _wrap(mod, name, cur, native))
+        setattr(mod, name, _wrap(mod, name, cur, native, mpmath))
         done.append(name)
     return done
 

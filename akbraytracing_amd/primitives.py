@@ -15,7 +15,9 @@ returns what the reference returns, including its value-level error rules:
 
 Results are bit-identical to the reference's numpy evaluation (fixtures in tests/golden).
 Inputs are converted to float64 (the reference's np.longdouble initial_params path, :14075, is
-not reproduced: fp64 only). There is no CPU fallback: without a GPU these raise.
+not reproduced: parameters stay float64). These are the numpy branch's functions; the option_mpmath
+branch of mirr_ray_intersection and reflect_ray (:399-443, :474-500) is extended.py (double-double
+arithmetic, that branch's value rules). There is no CPU fallback: without a GPU these raise.
 """
 import numpy as np
 import torch

@@ -68,7 +68,12 @@ class ChainLaunch:
 
     def __init__(self, mirrors, *, tan_h=None, tan_v=None, row0=0, n_rays=None, dirs=None, src=(0.0, 0.0, 0.0),
                  det_ghij=None, want=("last_hit", "dir_out"), samples=None, out=None, sink=None, flags=None,
-                 samples_buf=None, pert=None, ray0=None):
+                 samples_buf=None, pert=None, ray0=None, precision="fp64"):
+        if precision not in ("fp64", "dd"):
+            raise ValueError('precision must be "fp64" or "dd"')
+        if precision == "dd" and (sink is not None or pert is not None):
+            raise ValueError('the double-double chain (precision="dd") has no fused sink or OPL perturbation')
+        self.precision = precision
         dev = D.device()
         desc = _lib.ChainDesc()
         _fill_desc(desc, mirrors, det_ghij)
@@ -165,7 +170,9 @@ class ChainLaunch:
     def launch(self, stream=None, reset_flags=True):
         if reset_flags:
             self.res.flags.zero_()
-        _lib.check(_lib.lib().akb_trace_chain_f64(self.desc, D.stream_handle(stream)))
+        L = _lib.lib()
+        fn = L.akb_trace_chain_dd_f64 if self.precision == "dd" else L.akb_trace_chain_f64
+        _lib.check(fn(self.desc, D.stream_handle(stream)))
         return self.res
 
 
@@ -184,20 +191,27 @@ def trace_chain(mirrors, *, stream=None, **kw):
     out: optional dict of preallocated tensors keyed like ChainOutputs fields (reused buffers).
     sink: optional reduce.LeafSink(5, n_rays, nan_mask=0b00011) fed with (arctan(Ry/Rx),
         arctan(Rz/Rx), det_x, det_y, det_z) — the tilt means without writing those rows.
+    precision: "fp64" (default), or "dd" for the reference's option_mpmath branch: intersection and
+        reflection in double-double, each rounded to float64, everything else the float64 chain's
+        (akb_trace_chain_dd_f64; per-ray NaN on a miss, no sink / pert).
     """
     return ChainLaunch(mirrors, **kw).launch(stream=stream, reset_flags=False)
 
 
-def staged_chain(mirrors, dirs, src, with_segments=False):
+def staged_chain(mirrors, dirs, src, with_segments=False, prims=None):
     """The chain as the reference runs it, one primitive per stage (exact value rules).
-    Used when the fused kernel flags a miss or a zero norm. dirs, src: (3, n) device tensors."""
+    Used when the fused kernel flags a miss or a zero norm. dirs, src: (3, n) device tensors.
+    prims: the primitives' namespace (default primitives; extended.prims for the option_mpmath
+    branch's double-double intersection and reflection)."""
+    if prims is None:
+        prims = P
     hits, segs = [], []
     ray, org = dirs, src
     for m in mirrors:
-        p = P.mirr_ray_intersection(m.coeffs, ray, org, negative=m.negative)
+        p = prims.mirr_ray_intersection(m.coeffs, ray, org, negative=m.negative)
         if with_segments:
-            segs.append(P.segment_length(org, p))
-        ray = P.reflect_ray(ray, P.norm_vector(m.coeffs, p))
+            segs.append(prims.segment_length(org, p))
+        ray = prims.reflect_ray(ray, prims.norm_vector(m.coeffs, p))
         org = p
         hits.append(p)
     return hits, ray, segs

@@ -249,9 +249,19 @@ class RayWave:
 
     NSLOTS = 4  # runs in flight: k (front), k-1 (its sums finishing), k-2 (tilt fused into k), k-3 (OPD fused into k)
 
-    def __init__(self, geometry, n, shard=None, comm=None, resample_pass=True, perturbation=None):
+    def __init__(self, geometry, n, shard=None, comm=None, resample_pass=True, perturbation=None, precision="fp64"):
         """perturbation: optional legendre.LegendrePerturbation added to every ray's pass-2 optical
-        path (BASELINE config 5's figure-error model)."""
+        path (BASELINE config 5's figure-error model).
+        precision: "fp64" (default), or "dd" for the reference's option_mpmath branch - both passes
+        through the double-double chain (trace_chain(precision="dd")), then the float64 reductions,
+        tilt and OPD. One process, no pipelining: run() only."""
+        if precision not in ("fp64", "dd"):
+            raise ValueError('precision must be "fp64" or "dd"')
+        if precision == "dd" and (shard is not None or comm is not None):
+            raise ValueError('precision="dd" runs in one process over the whole grid: no shard / comm')
+        if precision == "dd" and perturbation is not None:
+            raise ValueError('precision="dd" has no OPL perturbation')
+        self.precision = precision
         self.g = geometry
         self.n = int(n)
         self.comm = comm or LocalComm()
@@ -487,6 +497,8 @@ class RayWave:
         them. A run is launch_back(launch_front()); a caller tracing several systems in a row can
         pass the previous run's launch_back as this run's overlap, so its tilt and OPD fill the
         GPU while the host resamples (bench.py does)."""
+        if self.precision == "dd":
+            return self._run_dd(opd, keep_rotated, full, geometry)
         return self.launch_back(self.launch_front(full=full, overlap=overlap, geometry=geometry,
                                                   next_geometry=next_geometry), opd=opd, keep_rotated=keep_rotated)
 
@@ -515,6 +527,8 @@ class RayWave:
         fused tilt / OPD of an earlier run keep that run's system (its front carries it).
         next_geometry: the system of the run after this one, whose picks prepass is queued here
         (default: this run's); announcing it keeps the prepass one run ahead."""
+        if self.precision == "dd":
+            raise ValueError('precision="dd" is not pipelined: call run()')
         L = _lib.lib()
         g = geometry if geometry is not None else self.g
         self._check_geometry(g)
@@ -743,6 +757,12 @@ class RayWave:
         rules) and the tilt from host-formed matrices."""
         torch.cuda.synchronize()
         last_hit, dir_out, det_pre, opl, atan = self._pass2_staged(tan_h2.clone(), tan_v2.clone(), g)
+        return self._after_pass2(last_hit, dir_out, det_pre, opl, atan, tan_h2, tan_v2, opd, keep_rotated, full,
+                                 slot, g)
+
+    def _after_pass2(self, last_hit, dir_out, det_pre, opl, atan, tan_h2, tan_v2, opd, keep_rotated, full, slot, g):
+        """From materialised pass-2 rows: the tilt means (numpy-order sums), host-formed tilt
+        matrices, the tilt and the OPD (:3583-3677)."""
         (atan_s, atan_c), (det_s, det_c) = self.sums(atan, nan=True), self.sums(det_pre)
         red = self.comm.allreduce_sums(torch.cat([atan_s, det_s, atan_c.to(D.F64), det_c.to(D.F64)]))
         host = red.cpu().numpy()
@@ -759,6 +779,39 @@ class RayWave:
             ry, rz = P.rotation_matrices(-theta_y, -theta_z)
             out.update(self._tilt_opd(last_hit, dir_out, opl, keep_rotated, full, host_tilt=(ry, rz, focus), slot=slot,
                                       g=g))
+        return out
+
+    def _run_dd(self, opd, keep_rotated, full, geometry=None):
+        """One run with both passes through the double-double chain (the reference with
+        option_mpmath set: only mirr_ray_intersection and reflect_ray change, :399-500): pass 1's
+        picks, the host resample, pass 2 with its rows materialised, then _run_staged's tail. A ray
+        that misses is NaN in its own columns (the branch's per-column rule) and drops out of the
+        nanmeans as in the reference; a flagged pass 1 raises as the float64 run does."""
+        from .trace import trace_chain
+        g = geometry if geometry is not None else self.g
+        self._check_geometry(g)
+        hb, he, col = self._plan
+        p1 = trace_chain(g.mirrors, tan_h=self.tan_h, tan_v=self.tan_v, src=g.source, want=(),
+                         samples=(hb, he, col), precision="dd")
+        host = p1.extra["samples"].cpu().numpy()
+        f1 = int(p1.flags.item())
+        if f1:
+            raise _lib.AKBError(self._pass1_error(f1))
+        nh = he - hb
+        if self.resample_pass:
+            th = np.tan(resample_axis(np.arctan(host[:nh]), self.rand_h))
+            tv = np.tan(resample_axis(np.arctan(host[nh:]), self.rand_v))
+        else:
+            th, tv = np.tan(self.rand_h), np.tan(self.rand_v)
+        tan_h2 = torch.from_numpy(th).to(self.dev)
+        tan_v2 = torch.from_numpy(tv).to(self.dev)
+        r = trace_chain(g.mirrors, tan_h=tan_h2, tan_v=tan_v2, src=g.source, det_ghij=g.det1,
+                        want=("last_hit", "dir_out", "opl", "det", "atan"), precision="dd")
+        out = self._after_pass2(r.last_hit, r.dir_out, r.det, r.opl, r.atan, tan_h2, tan_v2, opd, keep_rotated, full,
+                                0, g)
+        out["flags"] = (f1, int(r.flags.item()))
+        out["slot"] = 0
+        self.last = out
         return out
 
     def _tilt_buffers(self, keep_rotated, full, g=None):

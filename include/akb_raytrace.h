@@ -21,6 +21,8 @@
  *   akb_plane_isect_f64  plane_ray_intersection  EllipseRaytrace3D.py:145-157, AKB_raytrace_20250312.py:873-885
  *   akb_seglen_f64       np.linalg.norm(b-a, axis=0)  AKB_raytrace_20250312.py:2884-2897, :3623, :3630
  *   akb_rotate_f64       rotate_vectors / rotate_points  AKB_raytrace_20250312.py:917-943
+ *   akb_isect_dd_f64     mirr_ray_intersection, option_mpmath branch   AKB_raytrace_20250312.py:399-443
+ *   akb_reflect_dd_f64   reflect_ray, option_mpmath branch             AKB_raytrace_20250312.py:474-500, :510-552
  *   akb_trace_chain_f64  the pass-1 / pass-2 mirror chains of plot_result_debug
  *                        AKB_raytrace_20250312.py:2694-2717 (ray grid), :2770-2845 (pass 1),
  *                        :2881-2905 (pass 2 + OPL segments); KB_debug :10952-10997
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define AKB_ABI_VERSION 17
+#define AKB_ABI_VERSION 18
 
 /* status codes */
 #define AKB_OK 0
@@ -52,6 +54,7 @@ extern "C" {
 #define AKB_E_HIP (-2)       /* HIP runtime error */
 #define AKB_E_FFT (-3)       /* rocFFT error */
 #define AKB_E_NOMEM (-4)     /* allocation failed */
+#define AKB_E_ARG AKB_E_INVALID /* a descriptor field the entry point does not implement */
 
 /* bits of the device int32 `flags` word written by the trace kernels */
 #define AKB_FLAG_MISS 0x1          /* some ray had discriminant D <= 0 (or NaN): ref :457 all-NaN rule */
@@ -99,6 +102,19 @@ int akb_normal_f64(const double coeffs[10], const double* pt, int64_t pt_ld, int
 int akb_reflect_f64(const double* dir, int64_t dir_ld, int64_t dir_inc, const double* nrm,
                     int64_t nrm_ld, int64_t nrm_inc, int64_t n, double* out, int64_t out_ld,
                     int normalize, int32_t* flags, void* stream);
+
+/* The two primitives of the reference's option_mpmath branch (AKB_raytrace_20250312.py:399-443,
+ * :474-500): float64 in and out, the arithmetic in between in double-double (csrc/akb_dd.h), each
+ * output rounded once. The branch's per-column value rules are applied by the kernel itself:
+ * akb_isect_dd_f64 writes a NaN column where D < 0 (D == 0 hits) and akb_reflect_dd_f64 leaves a
+ * zero-norm column unnormalised; AKB_FLAG_MISS / AKB_FLAG_ZERO_REFLECT then mean "some column",
+ * for information only. Arguments as akb_isect_f64 / akb_reflect_f64 (no `normalize` switch). */
+int akb_isect_dd_f64(const double coeffs[10], const double* dir, int64_t dir_ld, int64_t dir_inc,
+                     const double* org, int64_t org_ld, int64_t org_inc, int negative, int64_t n,
+                     double* out, int64_t out_ld, int32_t* flags, void* stream);
+int akb_reflect_dd_f64(const double* dir, int64_t dir_ld, int64_t dir_inc, const double* nrm,
+                       int64_t nrm_ld, int64_t nrm_inc, int64_t n, double* out, int64_t out_ld,
+                       int32_t* flags, void* stream);
 
 /* normalize_vector: out = v / ||v|| ; ORs AKB_FLAG_ZERO_DIR if any ||v|| == 0 (caller keeps v). */
 int akb_normalize_f64(const double* v, int64_t v_ld, int64_t v_inc, int64_t n, double* out,
@@ -204,6 +220,16 @@ typedef struct akb_chain_desc {
 } akb_chain_desc;
 
 int akb_trace_chain_f64(const akb_chain_desc* desc, void* stream);
+/* The chain as the reference runs it with option_mpmath set: per mirror the double-double
+ * intersection (akb_isect_dd_f64's arithmetic) rounded to float64, the float64 normal
+ * (akb_normal_f64's), the double-double reflection (akb_reflect_dd_f64's) rounded to float64; the
+ * segment lengths, their left-to-right sum, the detector plane and the arctan rows are the float64
+ * operations of akb_trace_chain_f64 on those rounded values. Every output is bit-identical to the
+ * stage entry points composed in that order. Same descriptor: grid or explicit directions, ray0 /
+ * n_rays, constant or per-ray origins; outputs hits, last_hit, dir_out, det_out, opl, atan_h / v,
+ * samp_h / v, flags (mirror k's bits shifted by 4k; a missed ray's columns are NaN from that mirror
+ * on). sink, pert_* and copy_* are not implemented: AKB_E_ARG. */
+int akb_trace_chain_dd_f64(const akb_chain_desc* desc, void* stream);
 /* sizeof(akb_chain_desc), for bindings to check their struct layout */
 int64_t akb_chain_desc_size(void);
 
