@@ -22,6 +22,12 @@ FaithfulPupil runs it for run after run without a host wait on the queuing threa
                 (akb_pupil_post_f64), and the pad-16 PSF (akb_psf_f64). All on the stream, no host
                 synchronisation; errors the reference would raise surface in Ticket.check().
 
+The host steps this pipeline shares with the ray-sharded one (faithful_dist.ShardedFaithfulPupil)
+exist once: PupilPipeline (the slot a begin takes, the post + PSF once the map exists, the end of a
+finish, close) and Ticket here; the flag words' raises, the pocket block's layout and the
+akb_gd_pockets call in griddata.py (raise_for_cell_flags, raise_for_pocket_status, pocket_offsets,
+build_pockets), next to the flag bits.
+
 The host-synchronous drop-ins (griddata.griddata, pupilmap.wave_pupil, psfcalc.psf_calc) stay the
 API for single calls; tests/test_faithful_gpu.py holds this pipeline to them and to the
 reference's own PSF.
@@ -34,9 +40,9 @@ import torch
 
 from . import _lib
 from . import device as D
-from .griddata import CONE_GUARD, CONE_SWEEPS, _F_NEG, _F_NONCONVEX, _F_NONFINITE, _F_NOT_DELAUNAY, _F_POCKET, _F_POS
-from .griddata import ConeNotConverged, CubicGrid, chebyshev_weights
-from .psf import psf_stack
+from .griddata import CONE_GUARD, CONE_SWEEPS, ConeNotConverged, CubicGrid, build_pockets, chebyshev_weights
+from .griddata import pocket_offsets, raise_for_cell_flags, raise_for_pocket_status
+from .psf import image_axes, psf_stack
 from .pupilmap import POST_PARAMS, pupil_post, pupil_post_check
 
 EUV = 13.5e-9  # option_energy 'EUV' (:1161-1162)
@@ -97,9 +103,16 @@ class ErrorLog:
 
 
 class Ticket:
-    """One run in the pipeline: its slot, the tensors it reads, the pocket job, then its results."""
+    """One run in either pipeline: its slot, the tensors it reads (y, z, f; the sharded pipeline keeps
+    them in its window instead), the pocket job, the error the sharded job returned as a value (err),
+    then its results."""
 
-    __slots__ = ("slot", "y", "z", "f", "job", "npock", "result", "h2d", "finished", "done", "log", "erow")
+    __slots__ = ("slot", "y", "z", "f", "job", "npock", "err", "result", "h2d", "finished", "done", "log", "erow")
+
+    def __init__(self, slot, log=None):
+        self.slot, self.log, self.finished = slot, log, False
+        self.y = self.z = self.f = self.job = self.npock = self.err = None
+        self.result = self.h2d = self.done = self.erow = None
 
     def ready(self):
         return self.job.done()
@@ -107,14 +120,13 @@ class Ticket:
     def check(self):
         """Raise as the host chain would (waits for the device): non-finite hits, a lattice that is
         not a convex unfolded grid, pockets that are not locally Delaunay, too few points for the
-        plane fits. Reads this run's own error words (ErrorLog), not the slot's current ones."""
+        plane fits. Reads this run's own error words (ErrorLog), not the slot's current ones. (The
+        one-process check; a sharded run's is ShardedFaithfulPupil.check.)"""
         self.job.result()
         if self.erow is None:  # begun, never finished: the pocket job's checks are all there is
             return
         w = self.log.read(*self.erow, self.done)
-        st = int(w[:1].view(np.int64)[0])
-        if st & (_F_NOT_DELAUNAY | _F_POCKET):
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+        raise_for_pocket_status(int(w[:1].view(np.int64)[0]))
         pupil_post_check(w[3:])
         cone_guard(w[2], w[3:])
 
@@ -131,7 +143,67 @@ def cone_guard(est, params):
                                f"range, bar {CONE_GUARD:g}); re-run with the converged gradients")
 
 
-class FaithfulPupil:
+def stream_of(stream):
+    return torch.cuda.current_stream() if stream is None else stream
+
+
+class PupilPipeline:
+    """The host steps FaithfulPupil and faithful_dist.ShardedFaithfulPupil share: the slot a begin
+    takes, the post and PSF once the map exists, the end of a finish. A subclass owns slots (dicts
+    with the slot's "last" ticket), _next, size, pad, lams, the shared buffers map / change / post /
+    psf, _done (their last writer's end event) and pool."""
+
+    def _take_slot(self, st, y, z, f):
+        """The next slot for a run that reads y, z, f on stream st, once its previous run is through:
+        finished on the host (its pinned buffers copied: h2d) and, on st, past its last reader."""
+        s = self.slots[self._next]
+        self._next = (self._next + 1) % len(self.slots)
+        prev = s["last"]
+        if prev is not None:
+            if not prev.finished:
+                raise RuntimeError(f"{type(self).__name__}: more runs begun than slots before a finish")
+            if prev.h2d is not None:
+                D.wait_event(prev.h2d)
+            if prev.done is not None:  # the slot's last reader, on any stream
+                st.wait_event(prev.done)
+        for a in (y, z, f):  # read on this stream now and in finish: not to be reused before
+            a.record_stream(st)
+        return s
+
+    def _post_psf(self, st, axes, psf_events=None, post_events=None):
+        """Queue the post (nanmean, plane fits, prefilter, rotation) and the PSF of self.map on st,
+        with the pitch of axes (gx | gy | extent | pitch); the optional (start, end) events around
+        each. Returns the result dict (the buffers are reused by the next call)."""
+        m = self.size
+        if post_events is not None:
+            post_events[0].record(st)
+        post = pupil_post(self.map[0], out=self.post, stream=st)
+        if post_events is not None:
+            post_events[1].record(st)
+        self.post = post
+        if psf_events is not None:
+            psf_events[0].record(st)
+        psf, _, _ = psf_stack(post["opd"], None, self.lams, None, pad_factor=self.pad, stream=st, out=self.psf,
+                              pitch=axes[2 * m + 4:2 * m + 6])
+        if psf_events is not None:
+            psf_events[1].record(st)
+        self.psf = psf
+        return dict(psf=psf, map=self.map[0], corrected=post["corrected"], rotated=post["rotated"],
+                    params=post["params"], axes=axes, change=self.change)
+
+    def _end(self, st):
+        """Record the shared map / post / psf buffers' last writer on st: a later finish on another
+        stream waits for it. Returns the event."""
+        self._done = torch.cuda.Event()
+        self._done.record(st)
+        return self._done
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+
+
+class FaithfulPupil(PupilPipeline):
     """The faithful pupil and PSF of runs traced on an n_v x n_h ray grid (see the module doc).
     size: the pupil grid (the bench's 128); pad: psf_calc's pad factor (16); slots: runs between
     begin and finish; workers: pocket builders running at once."""
@@ -147,19 +219,15 @@ class FaithfulPupil:
         self.L = 2 * (self.nh - 1) + 2 * (self.nv - 1)
         nc = (self.nv - 1) * (self.nh - 1)
         Lr = self.L
-        cap = Lr
-        # pocket arrays in one int32 block: tri (3 cap) | nbr (3 cap) | edge (L) | xptr (L + 1) | xidx (6 cap) | npk
-        self._o = dict(tri=0, nbr=3 * cap, edge=6 * cap, xptr=6 * cap + Lr, xidx=6 * cap + 2 * Lr + 1)
-        self._o["npk"] = self._o["xidx"] + 6 * cap
-        self._pk_len = self._o["npk"] + 1
+        self._o = pocket_offsets(Lr)  # the pocket arrays in one int32 block
         self.slots = []
         for _ in range(int(slots)):
             self.slots.append(dict(
                 diag=torch.empty(nc, dtype=torch.uint8, device=self.dev),
                 ring=torch.zeros(2 * Lr + 1, dtype=D.F64, device=self.dev),
                 ring_host=torch.empty(2 * Lr + 1, dtype=D.F64, pin_memory=True),
-                pk_host=torch.zeros(self._pk_len, dtype=torch.int32, pin_memory=True),
-                pk=torch.zeros(self._pk_len, dtype=torch.int32, device=self.dev),
+                pk_host=torch.zeros(self._o["len"], dtype=torch.int32, pin_memory=True),
+                pk=torch.zeros(self._o["len"], dtype=torch.int32, device=self.dev),
                 owner=torch.empty(self.size * self.size, dtype=torch.int32, device=self.dev),
                 axes=torch.empty(2 * self.size + 6, dtype=D.F64, device=self.dev),  # gx | gy | extent | pitch
                 last=None))
@@ -190,23 +258,12 @@ class FaithfulPupil:
         """Queue the cell pass of one run's detector hits (y, z: (n,) device rows, e.g. detcenter2[1],
         [2]; f: its Wave2) on `stream` and start its pocket job. Returns a Ticket."""
         L = _lib.lib()
-        s = self.slots[self._next]
-        self._next = (self._next + 1) % len(self.slots)
-        if s["last"] is not None:  # the slot's previous run must be through its finish (pinned buffers)
-            prev = s["last"]
-            if not prev.finished:
-                raise RuntimeError("FaithfulPupil: more runs begun than slots before a finish")
-            if prev.h2d is not None:
-                D.wait_event(prev.h2d)
-        sh = D.stream_handle(stream)
+        st = stream_of(stream)
+        sh = D.stream_handle(st)
+        s = self._take_slot(st, y, z, f)
         Lr = self.L
         ring = s["ring"]
         flags = ring.view(torch.int32)[4 * Lr:4 * Lr + 1]
-        st = torch.cuda.current_stream() if stream is None else stream
-        if s["last"] is not None and s["last"].done is not None:  # the slot's last reader, on any stream
-            st.wait_event(s["last"].done)
-        for a in (y, z, f):  # read on this stream now and in finish: not to be reused before
-            a.record_stream(st)
         m = self.size
         gx, gy = s["axes"][:m], s["axes"][m:2 * m]
         with torch.cuda.stream(st):
@@ -220,9 +277,8 @@ class FaithfulPupil:
             s["ring_host"].copy_(ring, non_blocking=True)  # the ring and the cell flags, one copy
             ev = torch.cuda.Event()
             ev.record(st)
-        t = Ticket()
-        t.slot, t.y, t.z, t.f = s, y, z, f
-        t.npock, t.result, t.h2d, t.finished, t.done, t.log, t.erow = None, None, None, False, None, self.errors, None
+        t = Ticket(s, self.errors)
+        t.y, t.z, t.f = y, z, f
         t.job = self.pool.submit(self._pockets, s, ev)
         s["last"] = t
         return t
@@ -231,30 +287,19 @@ class FaithfulPupil:
         """Worker thread: wait for the ring and the cell flags on the host, build the pockets, check
         the flags - their errors first, as the host chain raises them."""
         ev.synchronize()
-        L = _lib.lib()
         Lr = self.L
         rb = s["ring_host"].numpy()
         err, npk = None, None
         if np.isfinite(rb[:2 * Lr]).all():
             buf = s["pk_host"].numpy()
-            o = self._o
-            hp = lambda k: buf[o[k]:].ctypes.data_as(_lib.c_vp)  # noqa: E731
             try:
                 t0 = time.perf_counter()
-                _lib.check(L.akb_gd_pockets(rb[:Lr].ctypes.data_as(_lib.c_vp), rb[Lr:2 * Lr].ctypes.data_as(_lib.c_vp),
-                                            self.nv, self.nh, Lr, hp("npk"), hp("tri"), hp("nbr"), hp("edge"),
-                                            hp("xptr"), hp("xidx")))
-                npk, s["po"] = pack_pockets(buf, o, Lr)
+                build_pockets(rb[:Lr], rb[Lr:2 * Lr], self.nv, self.nh, buf, self._o)
+                npk, s["po"] = pack_pockets(buf, self._o, Lr)
                 self.pocket_ms.append((time.perf_counter() - t0) * 1e3)  # (the host's pocket job, bench.py)
             except _lib.AKBError as e:
                 err = e
-        fl = int(rb[2 * Lr:].view(np.int32)[0])
-        if fl & _F_NONFINITE:
-            raise ValueError("griddata: non-finite point coordinates (a ray that missed)")
-        if fl & _F_NONCONVEX or (fl & _F_POS and fl & _F_NEG):
-            raise _lib.AKBError("griddata: the points do not form a convex, unfolded lattice")
-        if fl & _F_NOT_DELAUNAY:
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+        raise_for_cell_flags(int(rb[2 * Lr:].view(np.int32)[0]))
         if err is not None:
             raise err
         return npk
@@ -276,7 +321,7 @@ class FaithfulPupil:
             t.finished = True
             raise
         s = t.slot
-        st = torch.cuda.current_stream() if stream is None else stream
+        st = stream_of(stream)
         sh = D.stream_handle(st)
         o, Lr = s["po"], self.L
         with torch.cuda.stream(st):
@@ -303,27 +348,11 @@ class FaithfulPupil:
             _lib.check(L.akb_gd_cone_solve_f64(*tri, D.ptr(xptr), D.ptr(xidx), D.ptr(gx), m, D.ptr(gy), m,
                                                D.ptr(t.f), 1, self.sweeps, self._omegas, D.ptr(self.work),
                                                D.ptr(s["owner"]), D.ptr(self.map), D.ptr(self.change), sh))
-            if post_events is not None:
-                post_events[0].record(st)
-            post = pupil_post(self.map[0], out=self.post, stream=st)
-            if post_events is not None:
-                post_events[1].record(st)
-            self.post = post
-            if psf_events is not None:
-                psf_events[0].record(st)
-            psf, _, _ = psf_stack(post["opd"], None, self.lams, None, pad_factor=self.pad, stream=st, out=self.psf,
-                                  pitch=axes[2 * m + 4:2 * m + 6])
-            if psf_events is not None:
-                psf_events[1].record(st)
-            self.psf = psf
+            t.result = self._post_psf(st, axes, psf_events, post_events)
             if events is not None:
                 events[1].record(st)
             t.erow = self.errors.record((self.words,), st)
-            t.done = torch.cuda.Event()
-            t.done.record(st)
-            self._done = t.done
-        t.result = dict(psf=psf, map=self.map[0], corrected=post["corrected"], rotated=post["rotated"],
-                        params=post["params"], axes=axes, change=self.change)
+            t.done = self._end(st)
         t.y = t.z = t.f = None
         t.finished = True
         self.finished += 1
@@ -344,33 +373,22 @@ class FaithfulPupil:
     def _converged(self, y, z, f, ax, stream=None):
         """The run's map from the global gradient iteration (host-synchronous) on the run's axes ax,
         then the same post and PSF on the device; the result in finish's buffers."""
-        st = torch.cuda.current_stream() if stream is None else stream
+        st = stream_of(stream)
         m = self.size
         with torch.cuda.stream(st):
             cg = CubicGrid(y, z, self.nv, self.nh, delaunay_tol=self.tol)
             self.map[0].copy_(cg.interp(f.reshape(1, -1), ax[:m], ax[m:2 * m])[0])
-            post = pupil_post(self.map[0], out=self.post, stream=st)
-            self.post = post
-            psf, _, _ = psf_stack(post["opd"], None, self.lams, None, pad_factor=self.pad, stream=st, out=self.psf,
-                                  pitch=ax[2 * m + 4:2 * m + 6])
-            self.psf = psf
-            # the shared map / post / psf buffers' last writer: a later finish on another stream waits
-            # for this one, not for the run's own (earlier) finish
-            self._done = torch.cuda.Event()
-            self._done.record(st)
-        pupil_post_check(post["params"])
-        return dict(psf=psf, map=self.map[0], corrected=post["corrected"], rotated=post["rotated"],
-                    params=post["params"], axes=ax, change=self.change, converged=True)
-
-    def close(self):
-        self.pool.shutdown(wait=True)
+            res = self._post_psf(st, ax)
+            # a later finish on another stream waits for this one, not for the run's own (earlier) finish
+            self._end(st)
+        pupil_post_check(res["params"])
+        return dict(res, converged=True)
 
 
 def image_axes_of(result, pad=16, wavelength=EUV, defocus=1e-2):
     """x_im, y_im of psf_calc for a finished result (host): the pupil pitch after the driver's
     grid_H -= mean (:3698) from the device axes."""
-    from .psf import image_axes
-    a = result["axes"].cpu().numpy()
+    a =result["axes"].cpu().numpy()
     m = (a.size - 6) // 2
     gh, gv = np.meshgrid(a[:m], a[m:2 * m])
     gh, gv = gh - np.mean(gh), gv - np.mean(gv)

@@ -23,7 +23,9 @@ The map, pupil and PSF are the one-process FaithfulPupil's bit for bit (tests/te
 ranks at 10000^2; tests/test_faithful_dist_gpu.py: 2 - 8 ranks at smaller grids). Collectives run
 in the same order on every rank, so the caller decides when a run finishes, identically on all
 ranks (a lag, not the band owner's pocket job). The plan and the data movement are plain torch and
-run on CPU with gloo (tests/test_faithful_dist_cpu.py).
+run on CPU with gloo (tests/test_faithful_dist_cpu.py). The slot guard, the ticket, the post + PSF
+tail and the host waits are FaithfulPupil's own (faithful.PupilPipeline, faithful.Ticket); what is
+written out here is what differs: the halo exchange, the collectives, the window pointers.
 """
 import concurrent.futures
 import ctypes
@@ -33,12 +35,14 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .faithful import ErrorLog, cone_guard, pack_pockets
-from .pupilmap import POST_PARAMS
-from .griddata import CONE_SWEEPS, _F_NEG, _F_NONCONVEX, _F_NONFINITE, _F_NOT_DELAUNAY, _F_POCKET, _F_POS
+from . import _lib
+from . import device as D
+from .dist import gather_to_root
+from .faithful import EUV, ErrorLog, PupilPipeline, Ticket, cone_guard, pack_pockets, stream_of
+from .griddata import CONE_SWEEPS, _F_NONFINITE, ConeNotConverged, CubicGrid, build_pockets, chebyshev_weights
+from .griddata import pocket_offsets, raise_for_cell_flags, raise_for_pocket_status
+from .pupilmap import POST_PARAMS, pupil_post_check
 from .wavefront import Shard
-
-EUV = 13.5e-9
 
 
 # ---------------------------------------------------------------------- the plan (host only)
@@ -262,23 +266,13 @@ def _all_reduce_min(comm, t, group=None):
 
 # ---------------------------------------------------------------------- the pipeline
 
-class DistTicket:
-    __slots__ = ("slot", "job", "npock", "err", "result", "h2d", "finished", "done", "erow")
-
-    def ready(self):
-        return self.job.done()
-
-
-class ShardedFaithfulPupil:
+class ShardedFaithfulPupil(PupilPipeline):
     """The faithful pupil / PSF of runs traced as Shard.split row shards of an n x n grid: every rank
     calls begin / finish for the same runs in the same order (comm: dist.TorchComm). slots: runs
     between begin and finish."""
 
     def __init__(self, n, comm, size=128, pad=16, wavelengths=(EUV,), sweeps=CONE_SWEEPS, root=0, slots=2,
                  workers=2, delaunay_tol=1e-10):
-        from . import _lib
-        from . import device as D
-        from .griddata import chebyshev_weights
         L = _lib.lib()
         self.comm = comm
         self.plan = p = ShardPlan.make(n, comm.world, comm.rank, sweeps, root)
@@ -293,10 +287,8 @@ class ShardedFaithfulPupil:
         n = self.n
         m = self.size * self.size
         self.Lr = 4 * (n - 1)
-        Lr, cap = self.Lr, self.Lr
-        # the pocket block (FaithfulPupil's layout): tri | nbr | edge | xptr | xidx | npk
-        self._o = dict(tri=0, nbr=3 * cap, edge=6 * cap, xptr=6 * cap + Lr, xidx=6 * cap + 2 * Lr + 1)
-        self._o["npk"] = self._o["xidx"] + 6 * cap
+        Lr = self.Lr
+        self._o = pocket_offsets(Lr)  # the pocket block (FaithfulPupil's layout)
         self.slots = []
         for _ in range(int(slots)):
             s = dict(win=torch.zeros((3, p.nrows * n), dtype=D.F64, device=self.dev),
@@ -306,8 +298,8 @@ class ShardedFaithfulPupil:
             if p.is_root:
                 s.update(ring=torch.zeros(2 * Lr + 1, dtype=D.F64, device=self.dev),
                          ring_host=torch.empty(2 * Lr + 1, dtype=D.F64, pin_memory=True),
-                         pk_host=torch.zeros(self._o["npk"] + 1, dtype=torch.int32, pin_memory=True),
-                         pk=torch.zeros(self._o["npk"] + 1, dtype=torch.int32, device=self.dev),
+                         pk_host=torch.zeros(self._o["len"], dtype=torch.int32, pin_memory=True),
+                         pk=torch.zeros(self._o["len"], dtype=torch.int32, device=self.dev),
                          status=torch.zeros(1, dtype=torch.int64, device=self.dev))
             self.slots.append(s)
         self._next = 0
@@ -340,31 +332,17 @@ class ShardedFaithfulPupil:
     # ------------------------------------------------------------------ stage 1
     def begin(self, y, z, f, stream=None):
         """y, z, f: this rank's rows (its Shard's rays) of detcenter2[1], [2] and Wave2 (device).
-        Returns a DistTicket."""
-        from . import _lib
-        from . import device as D
+        Returns a faithful.Ticket (its y, z, f unused: the rows live in the slot's window)."""
         L = _lib.lib()
         p, n = self.plan, self.n
         if y.shape[0] != p.own[1] - p.own[0]:
             raise ValueError(f"rank {p.rank} holds rays [{p.own[0]}, {p.own[1]}): got {y.shape[0]} rows")
-        s = self.slots[self._next]
-        self._next = (self._next + 1) % len(self.slots)
-        if s["last"] is not None:
-            prev = s["last"]
-            if not prev.finished:
-                raise RuntimeError("ShardedFaithfulPupil: more runs begun than slots before a finish")
-            if prev.h2d is not None:
-                prev.h2d.synchronize()
-        st = torch.cuda.current_stream() if stream is None else stream
+        st = stream_of(stream)
         sh = D.stream_handle(st)
+        s = self._take_slot(st, y, z, f)
         win, diag = s["win"], s["diag"]
-        t = DistTicket()
-        t.slot, t.npock, t.err, t.result, t.h2d, t.finished, t.done, t.erow = s, 0, None, None, None, False, None, None
+        t = Ticket(s)
         with torch.cuda.stream(st):
-            if s["last"] is not None and s["last"].done is not None:  # the slot's last reader
-                st.wait_event(s["last"].done)
-            for a in (y, z, f):  # read on this stream (the trace allocated them on its own)
-                a.record_stream(st)
             exchange_halo(p, self.comm, torch.stack([y, z, f]), win, self.group)
             off = p.base * n
             s["flags"].zero_()
@@ -392,19 +370,14 @@ class ShardedFaithfulPupil:
     def _pockets(self, s, ev):
         """Worker thread on the band owner: the pockets from the ring. An error comes back as a value
         (every rank still runs finish's collectives) with the pocket block left empty."""
-        from . import _lib
         ev.synchronize()
-        L = _lib.lib()
         Lr, o = self.Lr, self._o
         buf = s["pk_host"].numpy()
         try:
             rb = s["ring_host"].numpy()
-            if int(rb[2 * Lr:].view(np.int32)[0]) & _F_NONFINITE:
-                raise ValueError("griddata: non-finite point coordinates (a ray that missed)")
-            hp = lambda k: buf[o[k]:].ctypes.data_as(_lib.c_vp)  # noqa: E731
-            _lib.check(L.akb_gd_pockets(rb[:Lr].ctypes.data_as(_lib.c_vp), rb[Lr:2 * Lr].ctypes.data_as(_lib.c_vp),
-                                        self.n, self.n, Lr, hp("npk"), hp("tri"), hp("nbr"), hp("edge"), hp("xptr"),
-                                        hp("xidx")))
+            # a missed ray only: the other flags wait for every rank's word (check)
+            raise_for_cell_flags(int(rb[2 * Lr:].view(np.int32)[0]) & _F_NONFINITE)
+            build_pockets(rb[:Lr], rb[Lr:2 * Lr], self.n, self.n, buf, o)
             npk, s["po"] = pack_pockets(buf, o, Lr)
             return npk, None
         except Exception as e:  # noqa: BLE001 - raised again by check()
@@ -419,15 +392,11 @@ class ShardedFaithfulPupil:
         """Queue the rest of t's chain. Returns dict(psf, map, corrected, rotated, params, axes,
         change) on the band owner, None elsewhere. events / psf_events: optional (start, end)
         timing events around the device work / the PSF alone (band owner)."""
-        from . import _lib
-        from . import device as D
-        from .psf import psf_stack
-        from .pupilmap import pupil_post
         L = _lib.lib()
         p, n, m, K = self.plan, self.n, self.size, self.K
-        t.npock, t.err = t.job.result()
+        t.npock, t.err = D.wait_result(t.job)
         s = t.slot
-        st = torch.cuda.current_stream() if stream is None else stream
+        st = stream_of(stream)
         sh = D.stream_handle(st)
         win, diag = s["win"], s["diag"]
         off = p.base * n
@@ -474,24 +443,12 @@ class ShardedFaithfulPupil:
                 s["rflags"].copy_(red[2 * mm:])
                 self.map.view(-1).copy_(red[:mm])
                 _lib.check(L.akb_gd_part_finish_f64(D.ptr(self.map), D.ptr(red[mm:2 * mm]), mm, 1, sh))
-                post = pupil_post(self.map[0], out=self.post, stream=st)
-                self.post = post
-                if psf_events is not None:
-                    psf_events[0].record(st)
-                psf, _, _ = psf_stack(post["opd"], None, self.lams, None, pad_factor=self.pad, stream=st,
-                                      out=self.psf, pitch=self.axes[2 * m + 4:2 * m + 6])
-                if psf_events is not None:
-                    psf_events[1].record(st)
-                self.psf = psf
-                res = dict(psf=psf, map=self.map[0], corrected=post["corrected"], rotated=post["rotated"],
-                           params=post["params"], axes=self.axes, change=self.change)
+                res = self._post_psf(st, self.axes, psf_events)
                 t.erow = self.errors.record((s["rflags"], s["status"].view(D.F64), self.change.view(D.F64),
-                                             post["params"]), st)  # rflags: the flags | the estimates
+                                             res["params"]), st)  # rflags: the flags | the estimates
             if events is not None:
                 events[1].record(st)
-            t.done = torch.cuda.Event()
-            t.done.record(st)
-            self._done = t.done
+            t.done = self._end(st)
         t.result = res
         t.finished = True
         self.finished += 1
@@ -502,8 +459,6 @@ class ShardedFaithfulPupil:
         lattice that is not a convex unfolded grid, pockets that are not locally Delaunay, too few
         points for the plane fits. The other ranks hold no result and return. Reads t's own error
         words (faithful.ErrorLog), not the slot's current ones."""
-        from . import _lib
-        from .pupilmap import pupil_post_check
         if not self.plan.is_root:
             return
         if t.err is not None:
@@ -518,14 +473,8 @@ class ShardedFaithfulPupil:
         est = float(np.max(w[world:2 * world]))  # every rank's interior targets
         w = np.concatenate([w[:world], w[2 * world:]])
         self.flags_all = fl
-        if fl & _F_NONFINITE:
-            raise ValueError("griddata: non-finite point coordinates (a ray that missed)")
-        if fl & _F_NONCONVEX or (fl & _F_POS and fl & _F_NEG):
-            raise _lib.AKBError("griddata: the points do not form a convex, unfolded lattice")
-        if fl & _F_NOT_DELAUNAY:
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
-        if int(w[world:world + 1].view(np.int64)[0]) & (_F_NOT_DELAUNAY | _F_POCKET):
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+        raise_for_cell_flags(fl)
+        raise_for_pocket_status(int(w[world:world + 1].view(np.int64)[0]))
         pupil_post_check(w[world + 3:])
         cone_guard(est, w[world + 3:])
 
@@ -537,7 +486,6 @@ class ShardedFaithfulPupil:
         sweeps to scipy's tolerance on the run's axes; the other ranks return None, as for every
         run. Any other error raises on the band owner only (after the run's collectives, so the
         group stays in step)."""
-        from .griddata import ConeNotConverged
         t = self.begin(y, z, f, stream)
         res = self.finish(t, stream)
         verdict, err = 0, None
@@ -561,32 +509,17 @@ class ShardedFaithfulPupil:
         """The guard's fallback (collective): every rank's rows to the band owner, which forms the
         run's map from the global gradient iteration (CubicGrid.interp) on the run's axes, then the
         same post and PSF; None on the other ranks."""
-        from . import device as D
-        from .dist import gather_to_root
-        from .griddata import CubicGrid
-        from .pupilmap import pupil_post, pupil_post_check
-        from .psf import psf_stack
         p, m = self.plan, self.size
         counts = [sh.count for sh in p.shards]
         got = gather_to_root(self.comm, [y.contiguous(), z.contiguous(), f.contiguous()], counts, p.root)
         if got is None:
             return None
-        st = torch.cuda.current_stream() if stream is None else stream
+        st = stream_of(stream)
         with torch.cuda.stream(st):
             ya, za, fa = got
             cg = CubicGrid(ya, za, self.n, self.n, delaunay_tol=self.tol)
             self.map[0].copy_(cg.interp(fa.reshape(1, -1), self.axes[:m], self.axes[m:2 * m])[0])
-            post = pupil_post(self.map[0], out=self.post, stream=st)
-            self.post = post
-            psf, _, _ = psf_stack(post["opd"], None, self.lams, None, pad_factor=self.pad, stream=st,
-                                  out=self.psf, pitch=self.axes[2 * m + 4:2 * m + 6])
-            self.psf = psf
-            self._done = torch.cuda.Event()  # the shared buffers' last writer (see FaithfulPupil._converged)
-            self._done.record(st)
-        pupil_post_check(post["params"])
-        return dict(psf=psf, map=self.map[0], corrected=post["corrected"], rotated=post["rotated"],
-                    params=post["params"], axes=self.axes, change=self.change, converged=True)
-
-    def close(self):
-        if self.pool is not None:
-            self.pool.shutdown(wait=True)
+            res = self._post_psf(st, self.axes)
+            self._end(st)  # the shared buffers' last writer (see FaithfulPupil._converged)
+        pupil_post_check(res["params"])
+        return dict(res, converged=True)

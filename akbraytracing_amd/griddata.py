@@ -25,6 +25,42 @@ from . import device as D
 
 _F_NONCONVEX, _F_NOT_DELAUNAY, _F_POCKET, _F_POS, _F_NEG, _F_NONFINITE = 1, 2, 4, 8, 16, 32
 
+
+def raise_for_cell_flags(fl):
+    """Raise for a cell pass's flag word as the reference's chain would: a missed ray first, then a
+    lattice that is not convex or turns both ways, then a cell pair that is not locally Delaunay."""
+    if fl & _F_NONFINITE:
+        raise ValueError("griddata: non-finite point coordinates (a ray that missed)")
+    if fl & _F_NONCONVEX or (fl & _F_POS and fl & _F_NEG):
+        raise _lib.AKBError("griddata: the points do not form a convex, unfolded lattice")
+    raise_for_pocket_status(fl & _F_NOT_DELAUNAY)
+
+
+def raise_for_pocket_status(st):
+    """Raise if the pockets' local-Delaunay check (akb_gd_check_pockets' status word) flagged them."""
+    if st & (_F_NOT_DELAUNAY | _F_POCKET):
+        raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+
+
+def pocket_offsets(Lr):
+    """The pocket block of a ring of Lr points, one int32 buffer at capacity (at most Lr pockets):
+    tri (3 cap) | nbr (3 cap) | edge (L) | xptr (L + 1) | xidx (6 cap) | npk. Returns the arrays'
+    offsets, the block's length under "len"."""
+    cap = Lr
+    o = dict(tri=0, nbr=3 * cap, edge=6 * cap, xptr=6 * cap + Lr, xidx=6 * cap + 2 * Lr + 1)
+    o["npk"] = o["xidx"] + 6 * cap
+    o["len"] = o["npk"] + 1
+    return o
+
+
+def build_pockets(rx, ry, n_v, n_h, buf, o):
+    """The hull pockets of the boundary ring (rx, ry: host float64) into the block buf (host int32)
+    at the offsets o = pocket_offsets(len(rx)): akb_gd_pockets, host C++."""
+    L = _lib.lib()
+    hp = lambda k: buf[o[k]:].ctypes.data_as(_lib.c_vp)  # noqa: E731
+    _lib.check(L.akb_gd_pockets(rx.ctypes.data_as(_lib.c_vp), ry.ctypes.data_as(_lib.c_vp), n_v, n_h, rx.size,
+                                hp("npk"), hp("tri"), hp("nbr"), hp("edge"), hp("xptr"), hp("xidx")))
+
 # Stopping tolerance of the gradient iteration: the largest relative change of a Jacobi step
 # (scipy's measure) below scipy's own tolerance, 1e-6. Its iterates and ours differ, so neither
 # point is the other's: what parity needs is the interpolated values near the common fixed point,
@@ -107,53 +143,36 @@ class CubicGrid:
                 self.diag[torch.from_numpy(cells.astype(np.int64)).to(self.dev)] = \
                     torch.from_numpy(splits.astype(np.uint8)).to(self.dev)
         rb = ringbuf.cpu().numpy()
-        f = int(rb[2 * self.L:].view(np.int32)[0])
-        if f & _F_NONFINITE:
-            raise ValueError("griddata: non-finite point coordinates (a ray that missed)")
-        if f & _F_NONCONVEX or (f & _F_POS and f & _F_NEG):
-            raise _lib.AKBError("griddata: the points do not form a convex, unfolded lattice")
-        if f & _F_NOT_DELAUNAY:
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+        raise_for_cell_flags(int(rb[2 * self.L:].view(np.int32)[0]))
         rx, ry = rb[:self.L], rb[self.L:2 * self.L]
-        # the point set's extent: an unfolded lattice's extremes lie on its boundary ring
+        # the point set's extent: the extremes of a lattice that is not folded lie on its boundary ring
         self.extent = (float(rx.min()), float(rx.max()), float(ry.min()), float(ry.max()))
-        cap = self.L
-        # tri (3 cap) | nbr (3 cap) | edge (L) | xptr (L + 1) | xidx (6 cap) | npk: one host buffer, one copy
-        o_tri, o_nbr, o_edge, o_xptr = 0, 3 * cap, 6 * cap, 6 * cap + self.L
-        o_xidx = o_xptr + self.L + 1
-        o_npk = o_xidx + 6 * cap
-        buf = np.zeros(o_npk + 1, np.int32)
-        hp = lambda o: buf[o:].ctypes.data_as(_lib.c_vp)  # noqa: E731
-        _lib.check(L.akb_gd_pockets(rx.ctypes.data_as(_lib.c_vp), ry.ctypes.data_as(_lib.c_vp), self.nv, self.nh,
-                                    cap, hp(o_npk), hp(o_tri), hp(o_nbr), hp(o_edge), hp(o_xptr), hp(o_xidx)))
-        self.npock = int(buf[o_npk])
+        o = pocket_offsets(self.L)
+        buf = np.zeros(o["len"], np.int32)  # one host buffer, one copy
+        build_pockets(rx, ry, self.nv, self.nh, buf, o)
+        self.npock = int(buf[o["npk"]])
         dbuf = torch.from_numpy(buf).to(self.dev)
         k = max(self.npock, 1)
-        self.ptri = dbuf[o_tri:o_tri + 3 * k]
-        self.pnbr = dbuf[o_nbr:o_nbr + 3 * k]
-        self.edge_tri = dbuf[o_edge:o_edge + self.L]
-        self.xptr = dbuf[o_xptr:o_xptr + self.L + 1]
-        self.xidx = dbuf[o_xidx:o_xidx + 6 * cap]
+        self.ptri = dbuf[o["tri"]:o["tri"] + 3 * k]
+        self.pnbr = dbuf[o["nbr"]:o["nbr"] + 3 * k]
+        self.edge_tri = dbuf[o["edge"]:o["edge"] + self.L]
+        self.xptr = dbuf[o["xptr"]:o["xptr"] + self.L + 1]
+        self.xidx = dbuf[o["xidx"]:o["npk"]]
         # the pockets' local-Delaunay check lands in a status word read with the first sweep batch
         self._status = torch.zeros(1, dtype=torch.int64, device=self.dev)
         _lib.check(L.akb_gd_check_pockets(D.ptr(self.x), D.ptr(self.y), self.nv, self.nh, D.ptr(self.diag),
                                           self.npock, D.ptr(self.ptri), D.ptr(self.pnbr), D.ptr(self.edge_tri),
                                           float(delaunay_tol), D.ptr(self._status), s))
         self._checked = False
-        self._bad = False
+        self._word = 0
         self.sweeps = 0
 
     def _check_status(self, word=None):
         """Raise if the pocket check flagged the triangulation (word: its value, already on the host)."""
-        if self._checked:
-            if self._bad:  # a flagged triangulation stays refused on every later call
-                raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
-            return
-        f = int(self._status.item()) if word is None else int(word)
-        self._checked = True
-        self._bad = bool(f & (_F_NOT_DELAUNAY | _F_POCKET))
-        if self._bad:
-            raise _lib.AKBError("griddata: the grid is too distorted for the structured Delaunay triangulation")
+        if not self._checked:
+            self._word = int(self._status.item()) if word is None else int(word)
+            self._checked = True
+        raise_for_pocket_status(self._word)  # a flagged triangulation stays refused on every later call
 
     def _tri_args(self):
         return (D.ptr(self.x), D.ptr(self.y), self.nv, self.nh, D.ptr(self.diag), self.npock, D.ptr(self.ptri),

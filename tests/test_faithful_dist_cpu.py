@@ -169,6 +169,45 @@ def test_halo_and_band_movement_gloo(tmp_path, n, world):
         assert got.size == (3 if r == 0 else 1)
 
 
+def _raised(fn, word):
+    try:
+        fn(word)
+    except Exception as e:  # noqa: BLE001 - the type is what is compared
+        return type(e), str(e)
+    return None, ""
+
+
+def test_flag_words_to_exceptions():
+    """The one policy from a flag word to the reference's raise, over every combination of the five
+    cell-flag bits and of the pocket status bits: non-finite hits first (ValueError), then a lattice
+    that is not convex or turns both ways, then a cell that is not locally Delaunay; a lattice that
+    turns one way only raises nothing. The pocket status word: either bit refuses the grid."""
+    from akbraytracing_amd import _lib
+    from akbraytracing_amd import griddata as G
+    bits = (G._F_NONCONVEX, G._F_NOT_DELAUNAY, G._F_POS, G._F_NEG, G._F_NONFINITE)
+    assert bits == (1, 2, 8, 16, 32) and G._F_POCKET == 4
+    words = [sum(b for i, b in enumerate(bits) if k >> i & 1) for k in range(32)]
+    assert len(set(words)) == 32
+    for fl in words:
+        if fl & 32:
+            want = (ValueError, "non-finite point coordinates")
+        elif fl & 1 or (fl & 8 and fl & 16):
+            want = (_lib.AKBError, "convex, unfolded lattice")
+        elif fl & 2:
+            want = (_lib.AKBError, "too distorted")
+        else:
+            want = (None, "")
+        kind, msg = _raised(G.raise_for_cell_flags, fl)
+        assert kind is want[0] and want[1] in msg, (fl, kind, msg)
+    assert _raised(G.raise_for_cell_flags, G._F_POS) == (None, "") and _raised(G.raise_for_cell_flags, G._F_NEG) == (None, "")
+    for st in range(8):  # non-convex | not Delaunay | pocket: the first is no pocket status bit
+        kind, msg = _raised(G.raise_for_pocket_status, st)
+        if st & (2 | 4):
+            assert kind is _lib.AKBError and "too distorted" in msg, st
+        else:
+            assert kind is None, st
+
+
 def test_pack_pockets_prefix():
     """faithful.pack_pockets: the device's pocket arrays packed into one prefix of the block
     (tri | nbr | edge | xptr | xidx[:xptr[L]]), the H2D copy's extent; the empty block too."""

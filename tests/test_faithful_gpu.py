@@ -114,6 +114,86 @@ def test_faithful_pipeline_raises_for_a_missed_ray(gpu):
     fp_.close()
 
 
+_SMALL = {}
+
+
+def _small_run():
+    """The 65^2 trace's hits and their PSF from a fresh one-slot pupil (formed once, left unchanged)."""
+    if not _SMALL:
+        from akbraytracing_amd.faithful import FaithfulPupil
+        n = 65
+        out = _trace(n)
+        y, z, w = out["detcenter2"][1].clone(), out["detcenter2"][2].clone(), out["wave2"].clone()
+        fp_ = FaithfulPupil(n, n, slots=1)
+        psf = fp_.run(y, z, w)["psf"].clone()
+        torch.cuda.synchronize()
+        fp_.close()
+        _SMALL.update(n=n, y=y, z=z, w=w, psf=psf)
+    return _SMALL
+
+
+def test_faithful_pipeline_refuses_more_runs_than_slots(gpu):
+    """A begin that would reuse a slot whose run is not through its finish raises, and leaves that
+    run as it was: it still finishes, checks clean and gives a fresh pupil's PSF bit for bit."""
+    from akbraytracing_amd.faithful import FaithfulPupil
+    c = _small_run()
+    fp_ = FaithfulPupil(c["n"], c["n"], slots=1)
+    t = fp_.begin(c["y"], c["z"], c["w"])
+    with pytest.raises(RuntimeError, match="more runs begun than slots"):
+        fp_.begin(c["y"], c["z"], c["w"])
+    r = fp_.finish(t)
+    t.check()
+    torch.cuda.synchronize()
+    assert torch.equal(r["psf"], c["psf"])
+    fp_.close()
+
+
+def test_faithful_pipeline_failed_run_leaves_its_slot_usable(gpu):
+    """finish of a run with one non-finite hit raises the host chain's ValueError and marks the
+    ticket finished; the same slot then carries a clean run to a fresh pupil's PSF bit for bit."""
+    from akbraytracing_amd.faithful import FaithfulPupil
+    c = _small_run()
+    n = c["n"]
+    y = c["y"].clone()
+    y[n * 10 + 5] = float("nan")
+    fp_ = FaithfulPupil(n, n, slots=1)
+    t = fp_.begin(y, c["z"], c["w"])
+    with pytest.raises(ValueError):
+        fp_.finish(t)
+    assert t.finished
+    r = fp_.run(c["y"], c["z"], c["w"])
+    torch.cuda.synchronize()
+    assert torch.equal(r["psf"], c["psf"])
+    fp_.close()
+
+
+def test_faithful_pipeline_records_its_timing_events(gpu):
+    """finish records the (start, end) pairs around the device work, the post and the PSF."""
+    from akbraytracing_amd.faithful import FaithfulPupil
+    c = _small_run()
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(3)]
+    fp_ = FaithfulPupil(c["n"], c["n"], slots=1)
+    t = fp_.begin(c["y"], c["z"], c["w"])
+    fp_.finish(t, events=pairs[0], psf_events=pairs[1], post_events=pairs[2])
+    torch.cuda.synchronize()
+    for e0, e1 in pairs:  # elapsed_time raises for an event that was never recorded
+        assert np.isfinite(e0.elapsed_time(e1))
+    fp_.close()
+
+
+def test_faithful_pipeline_ticket_begun_and_never_finished(gpu):
+    """check() of a ticket that never went through finish returns once its pocket job is done (the
+    job's own checks are all there is), and close() returns with that run still unfinished."""
+    from akbraytracing_amd.faithful import FaithfulPupil
+    c = _small_run()
+    fp_ = FaithfulPupil(c["n"], c["n"], slots=1)
+    t = fp_.begin(c["y"], c["z"], c["w"])
+    t.check()
+    assert t.ready() and not t.finished and t.erow is None
+    fp_.close()
+    torch.cuda.synchronize()
+
+
 def _guard_case(geom, n, sweeps=None):
     """One run of geom at n^2 through FaithfulPupil: (its map and value-error estimate, the map from
     the converged gradients on the same axes, the map's range)."""
