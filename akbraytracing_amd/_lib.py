@@ -20,13 +20,14 @@ c_int = ctypes.c_int
 c_dbl = ctypes.c_double
 c_vp = ctypes.c_void_p
 MAX_MIRRORS = 7
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 FLAG_MISS = 0x1
 FLAG_ZERO_NORMAL = 0x2
 FLAG_ZERO_REFLECT = 0x4
 FLAG_ZERO_DIR = 0x8
 FLAG_CHAIN_DIR = 1 << 28
+FLAG_FIG_OUTSIDE = 0x8  # mirror k's at << 4k in a chain's flag word
 
 # every symbol the header declares (tests check the library exports all of them)
 EXPORTS = [
@@ -34,7 +35,7 @@ EXPORTS = [
     "akb_stream_create_reserved", "akb_stream_destroy", "akb_reserved_cu_mask",
     "akb_isect_f64", "akb_normal_f64", "akb_reflect_f64", "akb_normalize_f64", "akb_plane_isect_f64",
     "akb_seglen_f64", "akb_rotate_f64", "akb_fill_nan_f64",
-    "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64",
+    "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64", "akb_figure_opl_f64",
     "akb_trace_chain_f64", "akb_chain_desc_size", "akb_tilt_opd_f64", "akb_tilt_params_f64",
     "akb_tilt_opd_dev_f64", "akb_chain_tilt_f64", "akb_chain_tilt_opd_f64", "akb_trace_chain_samples_f64", "akb_opd_f64", "akb_resample_f64", "akb_plane_sweep_rows_f64",
     "akb_plane_sweep_sink_f64",
@@ -65,6 +66,16 @@ class LeafSink(ctypes.Structure):
     ]
 
 
+class FigureMapDesc(ctypes.Structure):
+    """akb_figure_map"""
+    _fields_ = [
+        ("table", c_vp),
+        ("origin", c_dbl * 3), ("e_u", c_dbl * 3), ("e_w", c_dbl * 3),
+        ("u0", c_dbl), ("du", c_dbl), ("w0", c_dbl), ("dw", c_dbl),
+        ("nu", c_i32), ("nw", c_i32),
+    ]
+
+
 class ChainDesc(ctypes.Structure):
     """akb_chain_desc"""
     _fields_ = [
@@ -91,6 +102,7 @@ class ChainDesc(ctypes.Structure):
         ("sink", LeafSink),
         ("pert_h", c_vp), ("pert_v", c_vp), ("pert_terms", c_i32),
         ("copy_src", c_vp), ("copy_dst", c_vp), ("copy_n", c_i64),
+        ("fig", FigureMapDesc * MAX_MIRRORS), ("fig_out", c_vp),
     ]
 
 
@@ -114,6 +126,7 @@ def _declare(L):
         "akb_isect_dd_f64": ([c_vp] + v3 + v3 + [c_int, c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_reflect_dd_f64": (v3 + v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_trace_chain_dd_f64": ([ctypes.POINTER(ChainDesc), c_vp], c_int),
+        "akb_figure_opl_f64": ([ctypes.POINTER(FigureMapDesc), c_vp] + v3 + v3 + [c_i64, c_vp, c_int, c_vp, c_vp], c_int),
         "akb_normalize_f64": (v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_plane_isect_f64": ([c_vp] + v3 + v3 + [c_i64, c_vp, c_i64, c_vp], c_int),
         "akb_seglen_f64": (v3 + v3 + [c_i64, c_vp, c_vp], c_int),

@@ -17,6 +17,7 @@
 
 #include "akb_common.h"
 #include "akb_dd.h"
+#include "akb_figure.h"
 #include "akb_pairwise.h"
 #include "akb_sincos.h"
 
@@ -130,6 +131,28 @@ __global__ void __launch_bounds__(kBlock) k_normalize(V3In v, int64_t n, V3Out o
         const double s = norm3(x, y, z);
         if (s == 0.0) fl |= AKB_FLAG_ZERO_DIR;
         out.store(i, x / s, y / s, z / s);
+    }
+    if (fl) atomicOr(flags, fl);
+}
+
+// one mirror's figure term from materialised hits and incoming directions (akb_figure.h): the unit
+// normal by k_normal's expressions, the map's frame and grid constants wave-uniform from the
+// argument segment, sixteen gathers per ray from a table that stays in L2
+__global__ void __launch_bounds__(kBlock) k_figure_opl(akb_fig::Map M, Quadric Q, V3In hit, V3In dir, int64_t n,
+                                                       double* out, int accumulate, int32_t* flags) {
+    int fl = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double x = hit.x(i), y = hit.y(i), z = hit.z(i);
+        double nx, ny, nz;
+        quadric_grad(Q, x, y, z, nx, ny, nz);
+        const double s = norm3(nx, ny, nz);
+        if (s == 0.0) fl |= AKB_FLAG_ZERO_NORMAL;
+        const double dn = akb_fig::dot_dn(dir.x(i), dir.y(i), dir.z(i), nx / s, ny / s, nz / s);
+        bool outside;
+        const double delta = akb_fig::eval(M, x, y, z, dn, &outside, nullptr, nullptr);
+        if (outside) fl |= AKB_FLAG_FIG_OUTSIDE;
+        out[i] = (accumulate ? out[i] : 0.0) + delta;
     }
     if (fl) atomicOr(flags, fl);
 }
@@ -446,6 +469,20 @@ struct ChainArgs {
     int64_t cp_n;
 };
 
+// the figure maps of a chain (akb_chain_desc.fig / fig_out); they travel only with the kernels
+// instantiated for them, so every other kernel's argument segment is what it was
+struct FigArgs {
+    akb_fig::Map m[AKB_MAX_MIRRORS];
+    double* out;
+};
+struct ChainArgsFig : ChainArgs {
+    FigArgs fig;
+};
+// the kernels with figure terms at 3 waves per SIMD (168 VGPRs): a mirror's sixteen samples and two
+// fractions (36 VGPRs) are live across the normal beside the ray's state, which at the plain chain's
+// 4 waves (128 VGPRs) spilled 32 to 176 B of scratch
+constexpr int kFigWaves = 3;
+
 // the launch's staging copy (akb_chain_desc.copy_*), by workgroup 0 ahead of its rays: sixteen
 // loads in flight per thread (the source may be host memory across PCIe)
 __device__ __forceinline__ void stage_copy(const ChainArgs& a) {
@@ -541,9 +578,16 @@ struct Ray {
 // miss and zero-normal tests need the hit and the gradient but nothing after them - the reflected
 // direction of a unit ray about a unit normal cannot have a zero norm, so its normalisation (and
 // the normal's) are skipped. The ray R is left as it came in.
-template <int kKind, bool kOPL, bool kHits, bool kUnitIn, bool kOrigin = false, bool kFlagsOnly = false>
+// kFig: the mirror's figure term (akb_figure.h) joins dfig when the mirror has a map F->h (a
+// wave-uniform test; the frame and grid constants are scalar loads from the argument segment like
+// the coefficients). The sixteen table gathers are issued together right behind the hit, ahead of the
+// normal's arithmetic, and are consumed behind the unit normal - they add no store and no wait inside
+// the normal. The instantiations without kFig compile exactly as before.
+template <int kKind, bool kOPL, bool kHits, bool kUnitIn, bool kOrigin = false, bool kFlagsOnly = false,
+          bool kFig = false>
 __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& opl, int k,
-                                            int& fl, double* hits, int64_t hits_ld, int lane) {
+                                            int& fl, double* hits, int64_t hits_ld, int lane,
+                                            const akb_fig::Map* F = nullptr, double* dfig = nullptr) {
     const double l = R.l, m = R.m, n = R.n, p = R.p, q = R.q, r = R.r;
     double A, B, C;
     if (kKind == kKindYFree) {
@@ -613,6 +657,16 @@ __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& op
         (h + hits_ld)[lane] = y;
         (h + 2 * hits_ld)[lane] = z;
     }
+    // figure map: locate the hit and issue the table loads
+    double fv[16], ftu = 0.0, ftw = 0.0;
+    bool fout = false;
+    const bool fig = kFig && F->h != nullptr;  // wave-uniform
+    if (kFig && fig) {
+        int32_t off[16];
+        fout = akb_fig::locate(*F, x, y, z, off, ftu, ftw);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) fv[c] = ld_off(F->h, (uint32_t)off[c] << 3);
+    }
     // unit normal
     double nx, ny = 0.0, nz = 0.0, sn, in;
     const int zbit = AKB_FLAG_ZERO_NORMAL << (4 * k);
@@ -633,6 +687,10 @@ __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& op
     nx = div_pos(nx, sn, in);
     if (kKind != kKindYFree) ny = div_pos(ny, sn, in);
     if (kKind != kKindZFree) nz = div_pos(nz, sn, in);
+    if (kFig && fig) {
+        wave_flag(fout, AKB_FLAG_FIG_OUTSIDE << (4 * k), fl);
+        *dfig = *dfig + akb_fig::path_term(akb_fig::combine(fv, ftu, ftw, fout), akb_fig::dot_dn(l, m, n, nx, ny, nz));
+    }
     // reflection
     double rx, ry, rz;
     if (kKind == kKindYFree) {
@@ -702,10 +760,15 @@ __device__ __forceinline__ void ray_tables(const ChainArgs& a, int64_t i, uint32
 // kFixed: pass 2's output set, known at compile time - last hit, exit direction and OPL rows, no
 // detector / arctan rows, hits or picks - so none of the optional rows is tested per segment (their
 // tests' masks were what overflowed the scalar registers into VGPR lanes).
+// kFig: the mirrors' figure terms (fg: the launch's maps), summed in mirror order into d_fig and
+// added to the path behind the perturbation, opl = (opl + d_pert) + d_fig; never with kLean.
 template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false, class Post = NoHook>
+          bool kFixed = false, bool kFig = false, class Post = NoHook>
 __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, int t, uint32_t iv, uint32_t ih,
-                                              double th, double tv, int& fl, double (&qv)[5], Post post = Post()) {
+                                              double th, double tv, int& fl, double (&qv)[5], Post post = Post(),
+                                              const FigArgs* fg = nullptr) {
+    static_assert(!(kFig && kLean), "the lean pass 1 carries no figure maps");
+    double dfig = 0.0;
     const int64_t i = i0 + t;
     const int64_t g = a.g0 + i * a.g_stride;
     double* const hits = kHits ? a.hits + i0 : nullptr;
@@ -747,11 +810,14 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
             k0 = 1;
         } else {
             if (a.kind[0] == kKindYFree)
-                mirror_step<kKindYFree, kOPL, kHits, kGrid, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
+                mirror_step<kKindYFree, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
             else if (a.kind[0] == kKindZFree)
-                mirror_step<kKindZFree, kOPL, kHits, kGrid, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
+                mirror_step<kKindZFree, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
             else
-                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
+                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
             k0 = 1;
         }
     }
@@ -761,11 +827,14 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
 #pragma unroll 1
     for (int k = k0; k < kend; ++k) {
         if (a.kind[k] == kKindYFree)  // wave-uniform branch
-            mirror_step<kKindYFree, kOPL, kHits, kGrid>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
+            mirror_step<kKindYFree, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
         else if (a.kind[k] == kKindZFree)
-            mirror_step<kKindZFree, kOPL, kHits, kGrid>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
+            mirror_step<kKindZFree, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
         else
-            mirror_step<kKindGeneral, kOPL, kHits, kGrid>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
+            mirror_step<kKindGeneral, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
     }
     if (kLean && kend >= k0) {  // the last mirror: its flags only
         const int k = kend;
@@ -783,11 +852,13 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
             d = __builtin_fma(a.pert_v[(int64_t)k * a.n_v + iv], a.pert_h[(int64_t)k * a.n_h + ih], d);
         opl = opl + d;
     }
+    if (kFig && kOPL) opl = opl + dfig;
     post();
     // only the flags leave a lean ray (chain_tilt refuses picks): nothing of it stays live across post()
     if (kLean) return;
     const uint32_t off = (uint32_t)t << 3;
     if (kOPL && (kFixed || a.opl)) st_off(a.opl + i0, off, opl);
+    if (kFig && fg->out) st_off(fg->out + i0, off, dfig);
     if (!kLean && (kFixed || a.last_hit)) {
         double* o = a.last_hit + i0;
         st_off(o, off, p);
@@ -829,12 +900,14 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
 
 // the same, loading its own table entries (the unpipelined kernels)
 template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false>
-__device__ __forceinline__ void chain_ray(const ChainArgs& a, int64_t i0, int t, int& fl, double (&qv)[5]) {
+          bool kFixed = false, bool kFig = false>
+__device__ __forceinline__ void chain_ray(const ChainArgs& a, int64_t i0, int t, int& fl, double (&qv)[5],
+                                          const FigArgs* fg = nullptr) {
     uint32_t iv = 0, ih = 0;
     double th = 0.0, tv = 0.0;
     if (kGrid) ray_tables(a, i0 + t, iv, ih, th, tv);
-    chain_ray_tab<kGrid, kOPL, kNeedQ, kHits, kLean, kPointSrc, kFixed>(a, i0, t, iv, ih, th, tv, fl, qv);
+    chain_ray_tab<kGrid, kOPL, kNeedQ, kHits, kLean, kPointSrc, kFixed, kFig>(a, i0, t, iv, ih, th, tv, fl, qv, NoHook(),
+                                                                            fg);
 }
 
 template <bool kGrid, bool kOPL, int kWaves, bool kHits = false, bool kPointSrc = false>
@@ -845,6 +918,18 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain(ChainArgs a) {
     const int t = threadIdx.x;
     for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
         if (i0 + t < a.n) chain_ray<kGrid, kOPL, false, kHits, false, kPointSrc>(a, i0, t, fl, qv);
+    if (fl) atomicOr(a.flags, fl);
+}
+
+// k_chain with the mirrors' figure terms (always with the OPL row)
+template <bool kGrid, bool kHits>
+__global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_fig(ChainArgsFig a) {
+    stage_copy(a);
+    int fl = 0;
+    double qv[5];
+    const int t = threadIdx.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
+        if (i0 + t < a.n) chain_ray<kGrid, true, false, kHits, false, false, false, true>(a, i0, t, fl, qv, &a.fig);
     if (fl) atomicOr(a.flags, fl);
 }
 
@@ -959,6 +1044,24 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_sink(ChainArgs a) {
         const bool valid = seg * kLeafSeg + t < a.n;
         double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
         if (valid) chain_ray<kGrid, kOPL, true, false, false, kPointSrc, kFixed>(a, seg * kLeafSeg, t, fl, qv);
+        leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);
+    }
+    if (fl) atomicOr(a.flags, fl);
+}
+
+// k_chain_sink with the mirrors' figure terms; kFixed (grid rays from the point source, RayWave's
+// pass-2 output set) as there
+template <bool kGrid, bool kFixed>
+__global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_sink_fig(ChainArgsFig a) {
+    stage_copy(a);
+    __shared__ LeafLds<5> L;
+    int fl = 0;
+    const int t = threadIdx.x;
+    const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;
+    for (int64_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+        const bool valid = seg * kLeafSeg + t < a.n;
+        double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (valid) chain_ray<kGrid, true, true, false, false, kFixed, kFixed, true>(a, seg * kLeafSeg, t, fl, qv, &a.fig);
         leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);
     }
     if (fl) atomicOr(a.flags, fl);
@@ -1896,6 +1999,109 @@ static int chain_args_from(const akb_chain_desc* d, ChainArgs& a, bool& empty) {
     return AKB_OK;
 }
 
+// does the descriptor ask for figure terms (a map on some mirror, or the fig_out row)?
+static bool desc_has_fig(const akb_chain_desc* d) {
+    if (d->fig_out) return true;
+    for (int k = 0; k < AKB_MAX_MIRRORS; ++k)
+        if (d->fig[k].table) return true;
+    return false;
+}
+
+// the entry points with no figure plumbing refuse such a descriptor before they launch anything
+#define AKB_REFUSE_FIG(d, who)                                                                          \
+    do {                                                                                                \
+        if ((d) != nullptr && desc_has_fig(d)) {                                                        \
+            set_error(who ": figure maps (fig / fig_out) are implemented by akb_trace_chain_f64 only"); \
+            return AKB_E_ARG;                                                                           \
+        }                                                                                               \
+    } while (0)
+
+static_assert(sizeof(akb_fig::Map) == sizeof(akb_figure_map), "akb_fig::Map mirrors akb_figure_map");
+
+// validate one map and copy it into the kernel's form
+static int fig_map_from(const akb_figure_map* m, akb_fig::Map& M) {
+    AKB_REQUIRE(m->table != nullptr, "figure map without a table");
+    AKB_REQUIRE(m->nu >= 1 && m->nw >= 1 && (int64_t)m->nu * m->nw < (1LL << 28), "figure map size out of range");
+    AKB_REQUIRE(m->du > 0.0 && m->dw > 0.0 && std::isfinite(m->du) && std::isfinite(m->dw) && std::isfinite(m->u0) &&
+                    std::isfinite(m->w0), "figure map pitch must be positive and its grid finite");
+    double uu = 0.0, ww = 0.0, uw = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        AKB_REQUIRE(std::isfinite(m->origin[k]), "figure map origin must be finite");
+        uu += m->e_u[k] * m->e_u[k];
+        ww += m->e_w[k] * m->e_w[k];
+        uw += m->e_u[k] * m->e_w[k];
+    }
+    AKB_REQUIRE(std::fabs(uu - 1.0) <= 1e-12 && std::fabs(ww - 1.0) <= 1e-12 && std::fabs(uw) <= 1e-12,
+                "figure map axes must be unit and orthogonal");
+    M.h = m->table;
+    for (int k = 0; k < 3; ++k) {
+        M.o[k] = m->origin[k];
+        M.eu[k] = m->e_u[k];
+        M.ew[k] = m->e_w[k];
+    }
+    M.u0 = m->u0;
+    M.du = m->du;
+    M.w0 = m->w0;
+    M.dw = m->dw;
+    M.nu = m->nu;
+    M.nw = m->nw;
+    return AKB_OK;
+}
+
+int akb_figure_opl_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                       int64_t hit_inc, const double* dir, int64_t dir_ld, int64_t dir_inc, int64_t n, double* out,
+                       int accumulate, int32_t* flags, void* stream) {
+    clear_error();
+    AKB_REQUIRE(map && coeffs && hit && dir && out && flags, "null pointer");
+    AKB_REQUIRE(n >= 0, "n < 0");
+    akb_fig::Map M;
+    const int st = fig_map_from(map, M);
+    if (st != AKB_OK) return st;
+    if (n == 0) return AKB_OK;
+    k_figure_opl<<<grid_for(n, 1, kStreamGridCap), kBlock, 0, (hipStream_t)stream>>>(
+        M, quadric_from(coeffs), v3in(hit, hit_ld, hit_inc), v3in(dir, dir_ld, dir_inc), n, out, accumulate, flags);
+    return launch_status("k_figure_opl");
+}
+
+// the chain with figure maps: its own kernels (k_chain_fig / k_chain_sink_fig), the plain chain's grids
+static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStream_t s) {
+    AKB_REQUIRE(d->opl != nullptr, "figure maps add to the optical path: the descriptor needs opl");
+    ChainArgsFig f{};
+    static_cast<ChainArgs&>(f) = a;
+    for (int k = 0; k < AKB_MAX_MIRRORS; ++k) {
+        if (!d->fig[k].table) continue;
+        AKB_REQUIRE(k < d->n_mirrors, "figure map on a mirror beyond n_mirrors");
+        const int st = fig_map_from(&d->fig[k], f.fig.m[k]);
+        if (st != AKB_OK) return st;
+    }
+    f.fig.out = d->fig_out;
+    const bool grid = d->dir == nullptr;
+    if (d->sink.nq > 0) {
+        const int64_t nseg = (d->n_rays + kLeafSeg - 1) / kLeafSeg;
+        const unsigned gs = (unsigned)(nseg < kChainGridCap ? nseg : kChainGridCap);
+        // RayWave's pass 2, as launch_chain picks it
+        const bool fixed = grid && a.org == nullptr && a.last_hit && a.dir_out && !a.det_out && !a.atan_h &&
+                           !a.atan_v && !a.samp_h && !a.samp_v && !a.hits;
+        if (fixed)
+            k_chain_sink_fig<true, true><<<gs, kBlock, 0, s>>>(f);
+        else if (grid)
+            k_chain_sink_fig<true, false><<<gs, kBlock, 0, s>>>(f);
+        else
+            k_chain_sink_fig<false, false><<<gs, kBlock, 0, s>>>(f);
+        return launch_status("k_chain_sink_fig");
+    }
+    const unsigned g = grid_for(d->n_rays, 1, kChainGridCap);
+    if (grid && a.hits)
+        k_chain_fig<true, true><<<g, kBlock, 0, s>>>(f);
+    else if (grid)
+        k_chain_fig<true, false><<<g, kBlock, 0, s>>>(f);
+    else if (a.hits)
+        k_chain_fig<false, true><<<g, kBlock, 0, s>>>(f);
+    else
+        k_chain_fig<false, false><<<g, kBlock, 0, s>>>(f);
+    return launch_status("k_chain_fig");
+}
+
 int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
     clear_error();
     ChainArgs a;
@@ -1905,6 +2111,7 @@ int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
     const bool grid = d->dir == nullptr;
     const bool sink = d->sink.nq > 0;
     hipStream_t s = (hipStream_t)stream;
+    if (desc_has_fig(d)) return launch_chain_fig(d, a, s);
     const int64_t gcap = kChainGridCap;
     const unsigned gsz = grid_for(d->n_rays, 1, gcap);
     const int w = kChainWaves;
@@ -1937,6 +2144,7 @@ int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
 
 int akb_trace_chain_dd_f64(const akb_chain_desc* d, void* stream) {
     clear_error();
+    AKB_REFUSE_FIG(d, "akb_trace_chain_dd_f64");
     ChainArgs a;
     bool empty;
     const int st = chain_args_from(d, a, empty);
@@ -2192,6 +2400,7 @@ int akb_tilt_opd_dev_f64(const double* d_params, const double det1_ghij[4], cons
 int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stream) {
     clear_error();
     AKB_REQUIRE(descs != nullptr && n_sys > 0 && n_sys <= 65535, "need 1..65535 descriptors");
+    for (int s = 0; s < n_sys; ++s) AKB_REFUSE_FIG(descs + s, "akb_trace_chain_batch_f64");
     std::vector<ChainArgs> args((size_t)n_sys);
     int64_t nmax = 0;
     for (int s = 0; s < n_sys; ++s) {
@@ -2233,6 +2442,7 @@ int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stre
 int akb_trace_chain_samples_f64(const akb_chain_desc* d, void* stream) {
     clear_error();
     AKB_REQUIRE(d != nullptr, "null descriptor");
+    AKB_REFUSE_FIG(d, "akb_trace_chain_samples_f64");
     ChainArgs a;
     bool empty;
     const int st = chain_args_from(d, a, empty);
@@ -2290,6 +2500,7 @@ static int chain_tilt(const akb_chain_desc* d, const double* d_params, const dou
                       const double det2_ghij[4], const double* dir, const double* pt, const double* opl, int64_t ld,
                       int64_t n, double* dir_rot, double* pt_rot, double* det1, double* det2, double* total1,
                       double* total2, const akb_leaf_sink* sink, const OpdRows* o, void* stream) {
+    AKB_REFUSE_FIG(d, "akb_chain_tilt_f64");
     AKB_REQUIRE(d && d_params && sink, "null pointer");
     ChainArgs a;
     bool empty;

@@ -39,7 +39,7 @@ def ray_wave_conditions(option_HighNA=True):
 
 def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), option_set=True, option_HighNA=True,
                          option_energy="EUV", option_AKB=True, directory=None, workdir=None, verbose=True,
-                         as_dict=False, option_legendre=True, option_mpmath=False):
+                         as_dict=False, option_legendre=True, option_mpmath=False, figure=None):
     """The 'ray_wave' mode with option_save=True for the AKB system built from params on a
     ray_num x ray_num grid. With option_legendre (the alignment loops' call) returns
     (inner_products, orders, pvs) as the reference (:3775); without it (the plotting run) writes the
@@ -50,7 +50,9 @@ def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), optio
     directory). as_dict: also return the intermediate maps (device tensors).
     option_mpmath: the reference's flag of that name (:92) - the system is built with the
     double-double intersection and reflection (extended.prims) and traced by
-    RayWave(precision="dd"); everything downstream is unchanged."""
+    RayWave(precision="dd"); everything downstream is unchanged.
+    figure: optional list with one figure.FigureMap or None per mirror (RayWave(figure=...)): measured
+    figure error on the surfaces, added to the optical path; None changes nothing."""
     from . import geometry as G
     from .affine import extract_affine_square_region
     from .psfcalc import psf_calc
@@ -70,9 +72,9 @@ def plot_result_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), optio
     b = dict(b, det2=[float(x) for x in det2], defocus_wave_m=defocus_wave)
     n = int(ray_num)
     if option_mpmath:
-        run = RayWave(SystemGeometry.from_dict(b), n, precision="dd").run()
+        run = RayWave(SystemGeometry.from_dict(b), n, precision="dd", figure=figure).run()
     else:
-        run = RayWave(SystemGeometry.from_dict(b), n).run()
+        run = RayWave(SystemGeometry.from_dict(b), n, figure=figure).run()
     m = wave_maps(run["detcenter2"], run["dist_err2"], run["wave2"], n, n)
     matrixWave2 = m["matrixWave2"].cpu().numpy()
     workdir = os.getcwd() if workdir is None else workdir
@@ -138,7 +140,7 @@ KB_RECTIFIED_SIZE = 256  # extract_affine_square_region(..., target_size=256), :
 
 def kb_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), designparams=None, option_HighNA=True,
                 option_energy="EUV", widesearch=False, option_legendre=True, directory=None, workdir=None,
-                verbose=True, as_dict=False):
+                verbose=True, as_dict=False, figure=None):
     """KB_debug(params, na_ratio_h, na_ratio_v, 'ray_wave', option_legendre, source_shift,
     option_save=True) (:11725-11879) for the KB pair of geometry.build_kb on a ray_num x ray_num
     grid: one trace (the mode takes no equal-angle resample, :11001), the np.mean tilt
@@ -151,7 +153,8 @@ def kb_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), designparams=N
     figures are not drawn); np.inf for an unbuildable system.
 
     The device trace is RayWave's with resample_pass=False, whose nanmeans are np.mean's bits when
-    no ray misses; a ray that misses makes the reference's np.mean NaN everywhere, and raises here."""
+    no ray misses; a ray that misses makes the reference's np.mean NaN everywhere, and raises here.
+    figure: optional list with one figure.FigureMap or None per mirror (RayWave(figure=...))."""
     from . import _lib
     from . import geometry as G
     from .affine import extract_affine_square_region
@@ -168,7 +171,7 @@ def kb_ray_wave(params, ray_num, *, source_shift=(0.0, 0.0, 0.0), designparams=N
     det2[9] = -(np.float64(b["s2f_middle"]) + np.float64(b["defocus"]) + defocus_wave)  # coeffs_det2, :11740-11742
     b = dict(b, det2=[float(x) for x in det2], defocus_wave_m=defocus_wave)
     n = int(ray_num)
-    run = RayWave(SystemGeometry.from_dict(b), n, resample_pass=False).run()
+    run = RayWave(SystemGeometry.from_dict(b), n, resample_pass=False, figure=figure).run()
     if bool(torch.isnan(run["wave2"]).any()):
         raise _lib.AKBError("KB 'ray_wave': a ray missed a mirror or the detector; the reference's np.mean "
                             "makes every value NaN there")

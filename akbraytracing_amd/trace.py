@@ -45,6 +45,7 @@ class ChainOutputs:
     atan: torch.Tensor = None        # (2, n) arctan(Ry/Rx), arctan(Rz/Rx)
     samp_h: torch.Tensor = None      # slope samples of the middle row
     samp_v: torch.Tensor = None      # slope samples of the middle column
+    fig_opl: torch.Tensor = None     # (n,)  sum of the mirrors' figure terms (already inside opl)
     extra: dict = field(default_factory=dict)
 
 
@@ -68,11 +69,16 @@ class ChainLaunch:
 
     def __init__(self, mirrors, *, tan_h=None, tan_v=None, row0=0, n_rays=None, dirs=None, src=(0.0, 0.0, 0.0),
                  det_ghij=None, want=("last_hit", "dir_out"), samples=None, out=None, sink=None, flags=None,
-                 samples_buf=None, pert=None, ray0=None, precision="fp64"):
+                 samples_buf=None, pert=None, ray0=None, precision="fp64", figure=None):
+        from .figure import check_figure
         if precision not in ("fp64", "dd"):
             raise ValueError('precision must be "fp64" or "dd"')
         if precision == "dd" and (sink is not None or pert is not None):
             raise ValueError('the double-double chain (precision="dd") has no fused sink or OPL perturbation')
+        figure = check_figure(figure, len(mirrors))
+        if precision == "dd" and (figure is not None or "fig_opl" in want):
+            raise ValueError('the double-double chain (precision="dd") has no fused figure maps: add the terms '
+                             'with figure.stage_terms from its hits')
         self.precision = precision
         dev = D.device()
         desc = _lib.ChainDesc()
@@ -164,6 +170,15 @@ class ChainLaunch:
                 raise ValueError("perturbation tables must be (terms, n_h) and (terms, n_v)")
             desc.pert_h, desc.pert_v, desc.pert_terms = D.ptr(ph), D.ptr(pv), int(ph.shape[0])
             self.keep += [ph, pv]
+        if figure is not None or "fig_opl" in want:
+            if "opl" not in want:
+                raise ValueError("figure maps add to the optical path: want must contain 'opl'")
+            for k, f in enumerate(figure or ()):
+                if f is not None:
+                    self.keep.append(f.fill(desc.fig[k], dev))
+            if "fig_opl" in want:
+                res.fig_opl = buf("fig_opl", (n,))
+                desc.fig_out = D.ptr(res.fig_opl)
         res.extra["buffers"] = out
         self.desc, self.res = desc, res
 
@@ -182,7 +197,10 @@ def trace_chain(mirrors, *, stream=None, **kw):
     Rays: either the grid (tan_h, tan_v device tensors; flat rays ray0 .. + n_rays, ray0 defaulting
     to row0 * n_h) or explicit
     `dirs` (3, n) device tensor. Source: a 3-vector (constant) or a (3, n) device tensor.
-    want: subset of {"hits", "last_hit", "dir_out", "det", "opl", "atan"}.
+    want: subset of {"hits", "last_hit", "dir_out", "det", "opl", "atan", "fig_opl"}.
+    figure: optional list with one figure.FigureMap or None per mirror: each mapped mirror adds
+        -2 h |d . N| to the ray's opl (csrc/akb_figure.h); "fig_opl" in want returns the terms' sum.
+        A hit outside a map contributes 0 and raises FLAG_FIG_OUTSIDE << 4k in the flag word.
     samples: (h_begin, h_end, v_col) flat-index range / column whose exit slopes to record.
     flags / samples_buf: optional caller-owned int32 flag word and float64 pick buffer (RayWave
         places the flag words right after the picks so one copy brings both to the host).

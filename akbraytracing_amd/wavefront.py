@@ -249,9 +249,18 @@ class RayWave:
 
     NSLOTS = 4  # runs in flight: k (front), k-1 (its sums finishing), k-2 (tilt fused into k), k-3 (OPD fused into k)
 
-    def __init__(self, geometry, n, shard=None, comm=None, resample_pass=True, perturbation=None, precision="fp64"):
+    def __init__(self, geometry, n, shard=None, comm=None, resample_pass=True, perturbation=None, precision="fp64",
+                 figure=None):
         """perturbation: optional legendre.LegendrePerturbation added to every ray's pass-2 optical
         path (BASELINE config 5's figure-error model).
+        figure: optional list with one figure.FigureMap or None per mirror - figure error on the
+        surfaces themselves: each mapped mirror adds -2 h |d . N| to the pass-2 optical path
+        (opl = (opl + perturbation) + fig_opl; pass 1, the picks and the resample are unchanged).
+        Pass 2 runs the fused chain's figure instantiation (shards and the pipelined launch_front /
+        launch_back included); the staged fallback and precision="dd" add the same terms with the
+        stage kernel from their materialised hits (the double-double run adds them to the OPD
+        maps centred, _add_figure_centred). The result gains fig_opl. A ray that hits
+        outside a map raises AKBError naming the mirror.
         precision: "fp64" (default), or "dd" for the reference's option_mpmath branch - both passes
         through the double-double chain (trace_chain(precision="dd")), then the float64 reductions,
         tilt and OPD. One process, no pipelining: run() only."""
@@ -261,6 +270,8 @@ class RayWave:
             raise ValueError('precision="dd" runs in one process over the whole grid: no shard / comm')
         if precision == "dd" and perturbation is not None:
             raise ValueError('precision="dd" has no OPL perturbation')
+        from .figure import check_figure
+        self._figure = check_figure(figure, len(geometry.mirrors))
         self.precision = precision
         self.g = geometry
         self.n = int(n)
@@ -362,12 +373,14 @@ class RayWave:
         key = (bool(want_rows), slot)
         if key not in self._p2:
             want = ("last_hit", "dir_out", "opl") + (("det", "atan") if want_rows else ())
+            if self._figure is not None:
+                want += ("fig_opl",)
             # each slot writes its own output rows: run k's are tilted inside run k+2's pass 1
             t2 = self._tan2[slot]
             self._p2[key] = ChainLaunch(self.g.mirrors, tan_h=t2[:self.n], tan_v=t2[self.n:],
                                         ray0=self.shard.start, n_rays=self.n_local, src=self.g.source,
                                         det_ghij=self.g.det1, want=want, sink=self._sink2[slot],
-                                        flags=self._flagw[slot, 1:2], pert=self._pert)
+                                        flags=self._flagw[slot, 1:2], pert=self._pert, figure=self._figure)
             self._desc_key[id(self._p2[key])] = geometry_key(self.g)
         return self._p2[key]
 
@@ -480,9 +493,22 @@ class RayWave:
         if self._pert is not None:
             ph, pv = self._pert
             opl = opl + (pv.T @ ph).reshape(-1)[lo:lo + self.n_local]
+        fig = None
+        if self._figure is not None:
+            fig = self._stage_figure(g, hits, dirs)
+            opl = opl + fig
         det = P.plane_ray_intersection([0] * 6 + list(g.det1), r4, hits[-1])
         atan = torch.stack([torch.atan(r4[1] / r4[0]), torch.atan(r4[2] / r4[0])])
-        return hits[-1], r4, det, opl, atan
+        return hits[-1], r4, det, opl, atan, fig
+
+    def _stage_figure(self, g, hits, dirs, prims=None):
+        """The figure terms of materialised hits by the stage kernel, mirror by mirror (the staged
+        fallback and the double-double run); a hit outside a map raises."""
+        from .figure import outside_error, stage_terms
+        fig, word = stage_terms(g.mirrors, self._figure, hits, dirs, prims=prims)
+        if word:
+            raise _lib.AKBError(outside_error(word))
+        return fig
 
     # -------------------------------------------------------------- one run
     def run(self, opd=True, keep_rotated=False, full=False, overlap=None, geometry=None, next_geometry=None):
@@ -730,11 +756,18 @@ class RayWave:
 
     def _launch_back(self, f, opd, keep_rotated):
         r = f.r
+        if self._figure is not None:  # a hit outside a map is an error, never a reason for the staged path
+            from .figure import outside_error
+            msg = outside_error(self._resolve(f)[1])
+            if msg:
+                raise _lib.AKBError(msg)
         if self._resolve(f)[1]:  # a flagged pass 2: the staged path (a fused tilt is discarded)
             out = self._run_staged(None, f.tan_h2, f.tan_v2, opd, keep_rotated, f.full, slot=f.slot, g=f.g)
         else:
             out = RunResult(last_hit=r.last_hit, dir_out=r.dir_out, opl=r.opl, tan_h2=f.tan_h2, tan_v2=f.tan_v2,
                             params=f.params)
+            if self._figure is not None:
+                out["fig_opl"] = r.fig_opl
             if f.full:
                 out.update(det_pre=r.det, atan=r.atan)
             if f.opd is not None:  # tilted and OPD-formed inside the two next runs' pass 1
@@ -756,9 +789,12 @@ class RayWave:
         """Pass 2 flagged a miss or a zero norm: redo it stage by stage (the reference's value
         rules) and the tilt from host-formed matrices."""
         torch.cuda.synchronize()
-        last_hit, dir_out, det_pre, opl, atan = self._pass2_staged(tan_h2.clone(), tan_v2.clone(), g)
-        return self._after_pass2(last_hit, dir_out, det_pre, opl, atan, tan_h2, tan_v2, opd, keep_rotated, full,
-                                 slot, g)
+        last_hit, dir_out, det_pre, opl, atan, fig = self._pass2_staged(tan_h2.clone(), tan_v2.clone(), g)
+        out = self._after_pass2(last_hit, dir_out, det_pre, opl, atan, tan_h2, tan_v2, opd, keep_rotated, full,
+                                slot, g)
+        if fig is not None:
+            out["fig_opl"] = fig
+        return out
 
     def _after_pass2(self, last_hit, dir_out, det_pre, opl, atan, tan_h2, tan_v2, opd, keep_rotated, full, slot, g):
         """From materialised pass-2 rows: the tilt means (numpy-order sums), host-formed tilt
@@ -805,14 +841,52 @@ class RayWave:
             th, tv = np.tan(self.rand_h), np.tan(self.rand_v)
         tan_h2 = torch.from_numpy(th).to(self.dev)
         tan_v2 = torch.from_numpy(tv).to(self.dev)
-        r = trace_chain(g.mirrors, tan_h=tan_h2, tan_v=tan_v2, src=g.source, det_ghij=g.det1,
-                        want=("last_hit", "dir_out", "opl", "det", "atan"), precision="dd")
+        want = ("last_hit", "dir_out", "opl", "det", "atan") + (("hits",) if self._figure is not None else ())
+        r = trace_chain(g.mirrors, tan_h=tan_h2, tan_v=tan_v2, src=g.source, det_ghij=g.det1, want=want,
+                        precision="dd")
+        fig = None
+        if self._figure is not None:
+            # the terms from the double-double hits, the incoming directions rebuilt as the chain forms
+            # them (normalised grid directions, then the double-double reflection of each mirror)
+            from .extended import prims
+            from .trace import grid_dirs
+            fig = self._stage_figure(g, [r.hits[k] for k in range(len(g.mirrors))], grid_dirs(tan_h2, tan_v2), prims)
         out = self._after_pass2(r.last_hit, r.dir_out, r.det, r.opl, r.atan, tan_h2, tan_v2, opd, keep_rotated, full,
                                 0, g)
+        if fig is not None:
+            self._add_figure_centred(out, fig)
         out["flags"] = (f1, int(r.flags.item()))
         out["slot"] = 0
         self.last = out
         return out
+
+    def _add_figure_centred(self, out, fig):
+        """The figure terms of the double-double run, added where they keep their precision. A term
+        is ~1e-10 m; added to the 146 m OPL row it is quantised to that row's ulp (2.8e-5 nm), and
+        the float64 mean of the total paths (numpy's sum of n numbers of 146 m, divided) moves by up
+        to another ulp - as much as the double-double trace is run to resolve. The OPD maps are
+        differences from their means, so the terms join them centred instead:
+            DistError' = DistError + (fig_opl - nanmean(fig_opl)) * 1e9,  Wave2' likewise,
+        the mean over the rays the total path's nanmean counts (numpy's summation order). The path
+        rows (opl, total, total2) and the means gain the terms rounded, for reporting."""
+        out["fig_opl"] = fig
+        out["opl"] = out["opl"] + fig
+        ref = out.get("total2")
+        if ref is None:  # run(opd=False): no OPD maps to correct
+            return
+        counted = torch.where(torch.isnan(ref), torch.full_like(fig, float("nan")), fig)
+        s, c = self.sums(counted, nan=True)
+        centred = (fig - s[0] / c[0].to(D.F64)) * 1e9
+        for k in ("dist_err", "dist_err2", "wave2"):
+            if out.get(k) is not None:
+                out[k] = out[k] + centred
+        for k in ("total", "total2"):
+            if out.get(k) is not None:
+                out[k] = out[k] + fig
+        sums, cnts = self._means5
+        sums = sums.clone()
+        sums[3:5] += s[0]
+        self._means5 = (sums, cnts)
 
     def _tilt_buffers(self, keep_rotated, full, g=None):
         """Output tensors of one tilt (allocated on the current stream)."""

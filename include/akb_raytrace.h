@@ -23,6 +23,8 @@
  *   akb_rotate_f64       rotate_vectors / rotate_points  AKB_raytrace_20250312.py:917-943
  *   akb_isect_dd_f64     mirr_ray_intersection, option_mpmath branch   AKB_raytrace_20250312.py:399-443
  *   akb_reflect_dd_f64   reflect_ray, option_mpmath branch             AKB_raytrace_20250312.py:474-500, :510-552
+ *   akb_figure_opl_f64   (no reference call: the measured figure error that compareCSV.py /
+ *                        surfacedetailAKB.py plot, fed back into the optical path; csrc/akb_figure.h)
  *   akb_trace_chain_f64  the pass-1 / pass-2 mirror chains of plot_result_debug
  *                        AKB_raytrace_20250312.py:2694-2717 (ray grid), :2770-2845 (pass 1),
  *                        :2881-2905 (pass 2 + OPL segments); KB_debug :10952-10997
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define AKB_ABI_VERSION 18
+#define AKB_ABI_VERSION 19
 
 /* status codes */
 #define AKB_OK 0
@@ -64,6 +66,9 @@ extern "C" {
 /* akb_trace_chain_f64 shifts the MISS/ZERO bits of mirror k by 4*k (k < 7); bit 28
  * (AKB_FLAG_CHAIN_DIR) marks a zero-norm generated initial direction */
 #define AKB_FLAG_CHAIN_DIR (1 << 28)
+/* some ray hit a mirror outside that mirror's figure map (its term is 0): akb_figure_opl_f64 ORs the
+ * bit as it stands, akb_trace_chain_f64 shifts mirror k's by 4*k like the MISS/ZERO bits */
+#define AKB_FLAG_FIG_OUTSIDE 0x8
 
 const char* akb_last_error(void);
 int akb_abi_version(void);
@@ -115,6 +120,28 @@ int akb_isect_dd_f64(const double coeffs[10], const double* dir, int64_t dir_ld,
 int akb_reflect_dd_f64(const double* dir, int64_t dir_ld, int64_t dir_inc, const double* nrm,
                        int64_t nrm_ld, int64_t nrm_inc, int64_t n, double* out, int64_t out_ld,
                        int32_t* flags, void* stream);
+
+/* A mirror's figure error as a height map in the mirror's own frame (csrc/akb_figure.h holds the
+ * model and every operation's order): origin and the unit, orthogonal axes e_u, e_w in lab
+ * coordinates, a row-major (nw, nu) device table of heights in metres sampled at u0 + i du, w0 + j dw
+ * (du, dw > 0; nu or nw = 1: a 1-D profile, constant along that axis; nu * nw < 2^28). table = NULL:
+ * no map. */
+typedef struct akb_figure_map {
+    const double* table;
+    double origin[3], e_u[3], e_w[3];
+    double u0, du, w0, dw;
+    int32_t nu, nw;
+} akb_figure_map;
+
+/* One mirror's figure term of the optical path for n rays from materialised hit points and unit
+ * incoming directions: delta = -2 h(hit) |dir . N| with N the unit normal of the quadric at the hit
+ * (akb_normal_f64's expressions) and h the map's Catmull-Rom interpolation (edge replicate).
+ * accumulate = 0: out[i] = 0 + delta; accumulate = 1: out[i] = out[i] + delta (a chain's terms are
+ * summed in mirror order). A hit outside the map contributes 0 and ORs AKB_FLAG_FIG_OUTSIDE into
+ * *flags; a NaN hit gives NaN and no flag; AKB_FLAG_ZERO_NORMAL as akb_normal_f64. */
+int akb_figure_opl_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                       int64_t hit_inc, const double* dir, int64_t dir_ld, int64_t dir_inc, int64_t n, double* out,
+                       int accumulate, int32_t* flags, void* stream);
 
 /* normalize_vector: out = v / ||v|| ; ORs AKB_FLAG_ZERO_DIR if any ||v|| == 0 (caller keeps v). */
 int akb_normalize_f64(const double* v, int64_t v_ld, int64_t v_inc, int64_t n, double* out,
@@ -217,6 +244,14 @@ typedef struct akb_chain_desc {
      * memory a later launch on the stream reads) - RayWave hands the next pass 2 its resampled
      * tables this way, with no copy packet between the two trace kernels */
     const double* copy_src; double* copy_dst; int64_t copy_n;
+    /* optional figure error on the mirrors themselves (needs opl): mirror k with fig[k].table != NULL
+     * adds delta_k = -2 h_k(hit_k) |dir_k . N_k| (akb_figure_opl_f64's value, bit for bit) to the ray's
+     * path, opl = (opl + perturbation) + d_fig with d_fig = ((0 + delta_0) + delta_1) + ... in mirror
+     * order over the mirrors that have a map; fig_out (optional, (n)) receives d_fig. A hit outside
+     * mirror k's map contributes 0 and raises AKB_FLAG_FIG_OUTSIDE << 4k. akb_trace_chain_f64 only:
+     * every other entry point that takes a descriptor refuses one with a map or fig_out (AKB_E_ARG) */
+    akb_figure_map fig[AKB_MAX_MIRRORS];
+    double* fig_out;
 } akb_chain_desc;
 
 int akb_trace_chain_f64(const akb_chain_desc* desc, void* stream);
@@ -228,7 +263,7 @@ int akb_trace_chain_f64(const akb_chain_desc* desc, void* stream);
  * stage entry points composed in that order. Same descriptor: grid or explicit directions, ray0 /
  * n_rays, constant or per-ray origins; outputs hits, last_hit, dir_out, det_out, opl, atan_h / v,
  * samp_h / v, flags (mirror k's bits shifted by 4k; a missed ray's columns are NaN from that mirror
- * on). sink, pert_* and copy_* are not implemented: AKB_E_ARG. */
+ * on). sink, pert_*, copy_* and fig / fig_out are not implemented: AKB_E_ARG. */
 int akb_trace_chain_dd_f64(const akb_chain_desc* desc, void* stream);
 /* sizeof(akb_chain_desc), for bindings to check their struct layout */
 int64_t akb_chain_desc_size(void);
