@@ -35,7 +35,7 @@ EXPORTS = [
     "akb_stream_create_reserved", "akb_stream_destroy", "akb_reserved_cu_mask",
     "akb_isect_f64", "akb_normal_f64", "akb_reflect_f64", "akb_normalize_f64", "akb_plane_isect_f64",
     "akb_seglen_f64", "akb_rotate_f64", "akb_fill_nan_f64",
-    "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64", "akb_figure_opl_f64",
+    "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64", "akb_figure_opl_f64", "akb_figure_normal_f64",
     "akb_trace_chain_f64", "akb_chain_desc_size", "akb_tilt_opd_f64", "akb_tilt_params_f64",
     "akb_tilt_opd_dev_f64", "akb_chain_tilt_f64", "akb_chain_tilt_opd_f64", "akb_trace_chain_samples_f64", "akb_opd_f64", "akb_resample_f64", "akb_plane_sweep_rows_f64",
     "akb_plane_sweep_sink_f64",
@@ -102,7 +102,7 @@ class ChainDesc(ctypes.Structure):
         ("sink", LeafSink),
         ("pert_h", c_vp), ("pert_v", c_vp), ("pert_terms", c_i32),
         ("copy_src", c_vp), ("copy_dst", c_vp), ("copy_n", c_i64),
-        ("fig", FigureMapDesc * MAX_MIRRORS), ("fig_out", c_vp),
+        ("fig", FigureMapDesc * MAX_MIRRORS), ("fig_out", c_vp), ("fig_slope", c_i32),
     ]
 
 
@@ -127,6 +127,8 @@ def _declare(L):
         "akb_reflect_dd_f64": (v3 + v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_trace_chain_dd_f64": ([ctypes.POINTER(ChainDesc), c_vp], c_int),
         "akb_figure_opl_f64": ([ctypes.POINTER(FigureMapDesc), c_vp] + v3 + v3 + [c_i64, c_vp, c_int, c_vp, c_vp], c_int),
+        "akb_figure_normal_f64": ([ctypes.POINTER(FigureMapDesc), c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
+                                   c_vp], c_int),
         "akb_normalize_f64": (v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_plane_isect_f64": ([c_vp] + v3 + v3 + [c_i64, c_vp, c_i64, c_vp], c_int),
         "akb_seglen_f64": (v3 + v3 + [c_i64, c_vp, c_vp], c_int),
@@ -227,7 +229,11 @@ def _declare(L):
                                       c_vp], c_int),
     }
     for name, (args, res) in sig.items():
-        f = getattr(L, name)
+        try:
+            f = getattr(L, name)
+        except AttributeError:
+            raise AKBError(f"the library lacks {name}: it was built from other sources, rebuild "
+                           "(python -m akbraytracing_amd.build)") from None
         f.argtypes = args
         f.restype = res
 

@@ -47,9 +47,15 @@ def _tables(built, n):
 
 class TracedSystems:
     """S systems traced on an n x n grid: exit directions and last hits (S, 3, n^2) on the device,
-    their tilt rotations (S, 18) and detector-plane offsets s2f_middle."""
+    their tilt rotations (S, 18) and detector-plane offsets s2f_middle.
 
-    def __init__(self, builts, ray_num=53, want_hits=False, tilt=True, theta_mean="nanmean"):
+    figure: None, one list of figure.FigureMap | None per mirror used for every system, or a callable
+    built -> such a list (sweeps that move the mirrors). The maps deflect the rays (slope error,
+    akb_chain_desc.fig_slope) - the mode has no path output. A hit outside a map raises
+    AKBError."""
+
+    def __init__(self, builts, ray_num=53, want_hits=False, tilt=True, theta_mean="nanmean", figure=None):
+        from .figure import check_figure, outside_error
         L = _lib.lib()
         if theta_mean not in ("nanmean", "mean"):
             raise ValueError("theta_mean is 'nanmean' (plot_result_debug) or 'mean' (KB_debug)")
@@ -68,6 +74,7 @@ class TracedSystems:
         self.hits = torch.empty((S, K, 3, N), dtype=D.F64, device=self.dev) if want_hits else None
         self.flags = torch.zeros(S, dtype=torch.int32, device=self.dev)
         tabs, keep = {}, []
+        self.figures = [check_figure(figure(b) if callable(figure) else figure, K) for b in self.builts]
         descs = (_lib.ChainDesc * S)()
         for s, b in enumerate(self.builts):
             key = (tuple(b["angle_h"].items()), tuple(b["angle_v"].items()))
@@ -93,10 +100,19 @@ class TracedSystems:
                 d.hits, d.hits_ld = D.ptr(self.hits[s]), N
             d.samp_v_col = -1
             d.flags = D.ptr(self.flags[s:s + 1])
+            if self.figures[s] is not None:
+                d.fig_slope = 1
+                for k, f in enumerate(self.figures[s]):
+                    if f is not None:
+                        keep.append(f.fill(d.fig[k], self.dev))
         self._tabs = tabs
+        self.descs, self._keep = descs, keep  # the launch can be repeated (scripts/bench_figure_slope.py)
         _lib.check(L.akb_trace_chain_batch_f64(descs, S, D.stream_handle()))
         flags = self.flags.cpu().numpy()
         for s in np.nonzero(flags)[0]:
+            msg = outside_error(int(flags[s]))
+            if msg:
+                raise _lib.AKBError(f"system {int(s)}: {msg}")
             self._staged(int(s), tabs, n)
         self.s2f = np.array([b["s2f_middle"] for b in self.builts], dtype=np.float64)
         self.rot = self._rotations() if tilt else None
@@ -109,7 +125,13 @@ class TracedSystems:
         from .trace import grid_dirs
         dirs = grid_dirs(th, tv)
         src = torch.tensor(b["source"], dtype=D.F64, device=self.dev).reshape(3, 1).expand(3, self.N).contiguous()
-        hits, ray, _ = staged_chain(G.mirrors_of(b), dirs, src)
+        if self.figures[s] is not None:
+            from .figure import outside_error, stage_normals
+            hits, ray, _, word = stage_normals(G.mirrors_of(b), self.figures[s], dirs, src)
+            if word:
+                raise _lib.AKBError(f"system {s}: {outside_error(word)}")
+        else:
+            hits, ray, _ = staged_chain(G.mirrors_of(b), dirs, src)
         self.dir[s].copy_(ray)
         self.pt[s].copy_(hits[-1])
         if self.hits is not None:
@@ -178,14 +200,15 @@ class TracedSystems:
 
 
 def plot_result_test(params, source_shift=(0.0, 0.0, 0.0), option_tilt=True, *, option_set=True, ray_num=53,
-                     as_torch=False):
+                     as_torch=False, figure=None):
     """plot_result_debug(params, 'test', source_shift=..., option_tilt=...) (:1326, 'test' mode):
     (vmirr_hyp, hmirr_hyp0, vmirr_ell, hmirr_ell, detcenter, angle) as numpy (3, 53^2) arrays, or
-    np.inf where the reference returns np.inf."""
+    np.inf where the reference returns np.inf. figure (no reference argument): TracedSystems' - figure
+    maps in trace order (a list, or a callable built -> list) that deflect the rays."""
     b = G.build_akb(params, source_shift=source_shift, option_set=option_set)
     if not isinstance(b, dict):
         return b
-    ts = TracedSystems([b], ray_num=ray_num, want_hits=True, tilt=option_tilt)
+    ts = TracedSystems([b], ray_num=ray_num, want_hits=True, tilt=option_tilt, figure=figure)
     _, _, det, ang = ts.evaluate(np.array([b["defocus"]]), want_rows=True)
     h = ts.hits[0]
     out = (h[0], h[3], h[1], h[2], det[0, 0], ang[0, 0])
@@ -194,16 +217,16 @@ def plot_result_test(params, source_shift=(0.0, 0.0, 0.0), option_tilt=True, *, 
     return tuple(x.cpu().numpy() for x in out)
 
 
-def kb_test(params, source_shift=(0.0, 0.0, 0.0), *, designparams=None, ray_num=53, as_torch=False):
+def kb_test(params, source_shift=(0.0, 0.0, 0.0), *, designparams=None, ray_num=53, as_torch=False, figure=None):
     """KB_debug(params, na_ratio_h, na_ratio_v, 'test') (:9742-12726; the NA ratios are unused):
     the KB pair of geometry.build_kb traced once, the detector hits tilted by the np.mean exit
     angles (always: the mode sets option_tilt = True, :11703-11717). Returns (vmirr_hyp, tilted
     hmirr_hyp, tilted detcenter, tilted angle) as numpy (3, n^2) arrays, or np.inf where the
-    reference returns np.inf."""
+    reference returns np.inf. figure: as plot_result_test's."""
     b = G.build_kb(params, source_shift=source_shift, designparams=designparams)
     if not isinstance(b, dict):
         return b
-    ts = TracedSystems([b], ray_num=ray_num, want_hits=True, tilt=True, theta_mean="mean")
+    ts = TracedSystems([b], ray_num=ray_num, want_hits=True, tilt=True, theta_mean="mean", figure=figure)
     _, _, det, ang = ts.evaluate(np.array([b["defocus"]]), want_rows=True)
     # the H hits rotated about the untilted spot's mean (:11708-11709), as rotate_points does
     det1 = np.array(b["det1"], dtype=np.float64)
@@ -222,19 +245,25 @@ class _SystemCache:
     system 'kb' builds KB_debug's pair (geometry.build_kb: no source shift - auto_focus_NA calls
     KB_debug without one - and always tilted by the np.mean angles)."""
 
-    def __init__(self, option_set, ray_num, system="akb", kb_design=None):
+    def __init__(self, option_set, ray_num, system="akb", kb_design=None, figure=None):
         if system not in ("akb", "kb"):
             raise ValueError("system is 'akb' or 'kb'")
         self.option_set, self.ray_num, self.system = option_set, ray_num, system
         self.kb_design = kb_design
+        self.figure = figure
         self._c = {}
 
     def get(self, params, source_shift, tilt):
         kb = self.system == "kb"
         if kb:
             source_shift, tilt = (0.0, 0.0, 0.0), True
+        # the figure argument, by identity. It is fixed for one cache (auto_focus_NA refuses a cache made
+        # for another), so it separates nothing here: it is in the key so that a key names everything
+        # its system depends on. figure is a list or a callable, not a one-shot iterator.
+        fkey = None if self.figure is None else (id(self.figure) if callable(self.figure)
+                                                 else tuple(id(f) for f in self.figure))
         key = (tuple(float(x) for x in np.asarray(params, dtype=np.float64)[1:]),
-               tuple(float(x) for x in source_shift), bool(tilt))
+               tuple(float(x) for x in source_shift), bool(tilt), fkey)
         ts = self._c.get(key)
         if ts is None:
             if kb:
@@ -245,7 +274,8 @@ class _SystemCache:
                 # the reference's plot_result_debug / KB_debug returns np.inf here and
                 # auto_focus_NA's unpacking of it raises
                 raise TypeError("cannot unpack non-iterable float object")
-            ts = TracedSystems([b], ray_num=self.ray_num, tilt=tilt, theta_mean="mean" if kb else "nanmean")
+            ts = TracedSystems([b], ray_num=self.ray_num, tilt=tilt, theta_mean="mean" if kb else "nanmean",
+                               figure=self.figure)
             if len(self._c) > 64:
                 self._c.clear()
             self._c[key] = ts
@@ -254,7 +284,8 @@ class _SystemCache:
 
 def auto_focus_NA(num_adj_astg, initial_params, na_ratio_h, na_ratio_v, option, option_param, option_disp='ray',
                   option_mode=False, source_shift0=[0., 0., 0.], option_legendre=False, *, widesearch=False,
-                  option_set=True, option_AKB=True, kb_design=None, driver=None, verbose=True, cache=None):
+                  option_set=True, option_AKB=True, kb_design=None, driver=None, verbose=True, cache=None,
+                  figure=None):
     """auto_focus_NA (AKB_raytrace_20250312.py:12746-12895) for the AKB system (option_AKB): the same
     ranges, steps, attempts, astigmatism updates and stopping rule, with every 100-value sweep of
     params[0] one device evaluation. initial_params is updated in place as the reference does.
@@ -264,8 +295,12 @@ def auto_focus_NA(num_adj_astg, initial_params, na_ratio_h, na_ratio_v, option, 
     tilted by the np.mean angles, :12784; kb_design: the module's KBdesign_7params, :100).
     driver: the reference module, used only for what follows the search when `option` or
     `option_legendre` asks for a display or 'ray_wave' run (those call its own plot_result_debug /
-    KB_debug; without a driver they raise)."""
-    cache = cache or _SystemCache(option_set, 53, "akb" if option_AKB else "kb", kb_design)
+    KB_debug; without a driver they raise).
+    figure (no reference argument): TracedSystems' - figure maps that deflect the rays of every sweep
+    (a callable built -> list follows mirrors the search moves); a cache passed in must carry the same."""
+    if cache is not None and getattr(cache, "figure", None) is not figure:
+        raise ValueError("the cache was made for another figure= argument")
+    cache = cache or _SystemCache(option_set, 53, "akb" if option_AKB else "kb", kb_design, figure=figure)
     if widesearch:
         a_min, a_max = -1 + initial_params[0].copy(), 1 + initial_params[0].copy()
         shrink_factor, num_adj_astg, max_attempts = 0.1, 300, 17
@@ -318,7 +353,8 @@ def auto_focus_NA(num_adj_astg, initial_params, na_ratio_h, na_ratio_v, option, 
         if attempt == max_attempts:
             print("Warning: Maximum attempts reached. Returning current best result.")
     if option_param == 'FoC':
-        return plot_result_test(initial_params, source_shift0, option_tilt=False, option_set=option_set)[4]
+        return plot_result_test(initial_params, source_shift0, option_tilt=False, option_set=option_set,
+                                figure=figure)[4]
     if option_legendre or option:
         if driver is None:
             raise NotImplementedError("the display / 'ray_wave' follow-up runs the reference's plot_result_debug: "
@@ -343,21 +379,21 @@ def auto_focus_NA(num_adj_astg, initial_params, na_ratio_h, na_ratio_v, option, 
 
 
 def calc_FoC(initial_params, range_h=[-5e-3, 5e-3, 15], range_v=[-5e-3, 5e-3, 15], *, option_set=True,
-             verbose=False):
+             verbose=False, figure=None):
     """calc_FoC (:13766-13793) without its plots: for each source shift (0, h, v) on the grid, the
     FoC-mode auto_focus_NA (which carries params[0] from one source to the next, as the reference's
     in-place updates do) and the untilted spot's mean position and extent. Returns a dict of the
-    (len(range_v), len(range_h)) arrays focuspointX/Y/Z, focussizeH/V."""
+    (len(range_v), len(range_h)) arrays focuspointX/Y/Z, focussizeH/V. figure: as auto_focus_NA's."""
     range_h = np.linspace(range_h[0], range_h[1], range_h[2])
     range_v = np.linspace(range_v[0], range_v[1], range_v[2])
     shape = (len(range_v), len(range_h))
     out = {k: np.zeros(shape) for k in ("focuspointX", "focuspointY", "focuspointZ", "focussizeH", "focussizeV")}
-    cache = _SystemCache(option_set, 53)
+    cache = _SystemCache(option_set, 53, figure=figure)
     for i in range(len(range_v)):
         for j in range(len(range_h)):
             S0 = [0., range_h[j], range_v[i]]
             det = auto_focus_NA(50, initial_params, 1, 1, True, 'FoC', option_mode='FoC', source_shift0=S0,
-                                option_set=option_set, verbose=verbose, cache=cache)
+                                option_set=option_set, verbose=verbose, cache=cache, figure=figure)
             fp = np.mean(det, axis=1)
             out["focuspointX"][i, j], out["focuspointY"][i, j], out["focuspointZ"][i, j] = fp
             out["focussizeH"][i, j] = np.max(det[1, :]) - np.min(det[1, :])

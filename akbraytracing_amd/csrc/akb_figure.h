@@ -28,6 +28,21 @@
 // the four indices are clamped as integers, so no load leaves the table for any coordinate - NaN,
 // +-inf and huge values included. A NaN coordinate (a missed ray) selects index 0 with NaN weights:
 // the term is NaN like the rest of the ray's row, and no flag is raised for it.
+//
+// Slope error (the ray-spot modes): the same sixteen samples and two fractions also give
+// the map's gradient, and the gradient turns the normal the reflection uses - no further load.
+//   derivative weights in Horner form (dweights() below; they sum to zero)
+//   hu = (((cw0 ru'_0 + cw1 ru'_1) + cw2 ru'_2) + cw3 ru'_3) / du with ru'_j row j combined with the
+//     derivative weights in u, in combine's association; hw likewise with the plain weights in u and
+//     the derivative weights in w, divided by dw; an axis with one sample has derivative +0 along it;
+//     a hit outside the map has hu = hw = +0; a NaN fraction gives NaN
+//   sigma = (d . N > 0) ? -1 : 1 (sigma N is the normal turned towards the incoming beam; positive h
+//     is a bump towards it), g = hu e_u + hw e_w component by component (gx = hu eux + hw ewx),
+//     N' = (N - sigma g) / sqrt((x^2 + y^2) + z^2) of the numerator - always normalised for a hit
+//     inside the map, N itself for a hit outside it. g is not projected onto the local tangent plane:
+//     e_u, e_w are the frame's, and across a footprint the quadric's normal turns by milliradians.
+//   N' replaces N in the reflection only (reflect_ray's order, A = (l nx + m ny) + n nz, all three
+//     components whatever the mirror's kind); the path term keeps the quadric's own N.
 #pragma once
 
 #include <math.h>
@@ -55,6 +70,14 @@ AKB_FIG_FN void weights(double t, double (&c)[4]) {
     c[1] = ((1.5 * t - 2.5) * t) * t + 1.0;
     c[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
     c[3] = ((0.5 * t - 0.5) * t) * t;
+}
+
+// d/dt of weights(): the derivative weights of the same four samples (they sum to zero)
+AKB_FIG_FN void dweights(double t, double (&c)[4]) {
+    c[0] = (-1.5 * t + 2.0) * t - 0.5;
+    c[1] = (4.5 * t - 5.0) * t;
+    c[2] = (-4.5 * t + 4.0) * t + 0.5;
+    c[3] = (1.5 * t - 1.0) * t;
 }
 
 // one axis: the four clamped sample indices and the fraction t; returns true for a coordinate
@@ -106,6 +129,38 @@ AKB_FIG_FN double combine(const double (&v)[16], double tu, double tw, bool outs
     return outside ? 0.0 : h;
 }
 
+// the map's gradient (dh/du, dh/dw) from the same sixteen samples and two fractions
+AKB_FIG_FN void gradient(const double (&v)[16], double tu, double tw, const Map& M, bool outside, double& hu,
+                         double& hw) {
+    double cu[4], cw[4], du[4], dw[4], r[4], rd[4];
+    weights(tu, cu);
+    weights(tw, cw);
+    dweights(tu, du);
+    dweights(tw, dw);
+    for (int j = 0; j < 4; ++j) {
+        r[j] = ((cu[0] * v[4 * j] + cu[1] * v[4 * j + 1]) + cu[2] * v[4 * j + 2]) + cu[3] * v[4 * j + 3];
+        rd[j] = ((du[0] * v[4 * j] + du[1] * v[4 * j + 1]) + du[2] * v[4 * j + 2]) + du[3] * v[4 * j + 3];
+    }
+    const double gu = (((cw[0] * rd[0] + cw[1] * rd[1]) + cw[2] * rd[2]) + cw[3] * rd[3]) / M.du;
+    const double gw = (((dw[0] * r[0] + dw[1] * r[1]) + dw[2] * r[2]) + dw[3] * r[3]) / M.dw;
+    hu = (outside || M.nu == 1) ? 0.0 : gu;
+    hw = (outside || M.nw == 1) ? 0.0 : gw;
+}
+
+// the deflected unit normal N' in place of the unit normal (nx, ny, nz); dn = d . N
+AKB_FIG_FN void deflect(double& nx, double& ny, double& nz, double dn, const Map& M, double hu, double hw,
+                        bool outside) {
+    const double sigma = dn > 0.0 ? -1.0 : 1.0;
+    const double gx = hu * M.eu[0] + hw * M.ew[0];
+    const double gy = hu * M.eu[1] + hw * M.ew[1];
+    const double gz = hu * M.eu[2] + hw * M.ew[2];
+    const double x = nx - sigma * gx, y = ny - sigma * gy, z = nz - sigma * gz;
+    const double s = sqrt((x * x + y * y) + z * z);
+    nx = outside ? nx : x / s;
+    ny = outside ? ny : y / s;
+    nz = outside ? nz : z / s;
+}
+
 // the path term from the height and d . n
 AKB_FIG_FN double path_term(double h, double dn) { return (-2.0 * h) * fabs(dn); }
 
@@ -128,6 +183,19 @@ AKB_FIG_FN double eval(const Map& M, double x, double y, double z, double dn, bo
     if (off_out)
         for (int k = 0; k < 16; ++k) off_out[k] = off[k];
     return path_term(h, dn);
+}
+
+// the deflected normal for one hit with the unit normal (nx, ny, nz) and the unit incoming direction
+// (l, m, n): N' in place; returns true for a hit outside the map (N untouched)
+AKB_FIG_FN bool eval_normal(const Map& M, double x, double y, double z, double l, double m, double n, double& nx,
+                            double& ny, double& nz) {
+    int32_t off[16];
+    double tu, tw, v[16], hu, hw;
+    const bool o = locate(M, x, y, z, off, tu, tw);
+    for (int k = 0; k < 16; ++k) v[k] = M.h[off[k]];
+    gradient(v, tu, tw, M, o, hu, hw);
+    deflect(nx, ny, nz, dot_dn(l, m, n, nx, ny, nz), M, hu, hw, o);
+    return o;
 }
 
 }  // namespace akb_fig

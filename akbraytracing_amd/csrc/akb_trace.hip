@@ -157,6 +157,28 @@ __global__ void __launch_bounds__(kBlock) k_figure_opl(akb_fig::Map M, Quadric Q
     if (fl) atomicOr(flags, fl);
 }
 
+// one mirror's deflected unit normal from materialised hits and unit incoming directions
+// (akb_figure.h's gradient and deflect): k_normal's unit normal turned by the map's slope, the
+// quadric's own unit normal for a hit outside the map. The same gathers as k_figure_opl.
+__global__ void __launch_bounds__(kBlock) k_figure_normal(akb_fig::Map M, Quadric Q, V3In hit, V3In dir, int64_t n,
+                                                          V3Out out, int32_t* flags) {
+    int fl = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double x = hit.x(i), y = hit.y(i), z = hit.z(i);
+        double nx, ny, nz;
+        quadric_grad(Q, x, y, z, nx, ny, nz);
+        const double s = norm3(nx, ny, nz);
+        if (s == 0.0) fl |= AKB_FLAG_ZERO_NORMAL;
+        nx = nx / s;
+        ny = ny / s;
+        nz = nz / s;
+        if (akb_fig::eval_normal(M, x, y, z, dir.x(i), dir.y(i), dir.z(i), nx, ny, nz)) fl |= AKB_FLAG_FIG_OUTSIDE;
+        out.store(i, nx, ny, nz);
+    }
+    if (fl) atomicOr(flags, fl);
+}
+
 __global__ void __launch_bounds__(kBlock) k_plane(double g, double h, double ii, double j, V3In dir,
                                                   V3In org, int64_t n, V3Out out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
@@ -583,8 +605,13 @@ struct Ray {
 // the coefficients). The sixteen table gathers are issued together right behind the hit, ahead of the
 // normal's arithmetic, and are consumed behind the unit normal - they add no store and no wait inside
 // the normal. The instantiations without kFig compile exactly as before.
+// kSlope (with kFig): a mapped mirror also deflects the ray (akb_figure.h's gradient and deflect): the
+// map's gradient is formed from the same sixteen samples where combine runs, behind the unit normal,
+// and the reflection takes the deflected normal N' in reflect_ray's general three-component form
+// whatever the mirror's kind (N' has all three components); the path term keeps the quadric's own
+// N and joins dfig only with kOPL. The instantiations without kSlope compile exactly as before.
 template <int kKind, bool kOPL, bool kHits, bool kUnitIn, bool kOrigin = false, bool kFlagsOnly = false,
-          bool kFig = false>
+          bool kFig = false, bool kSlope = false>
 __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& opl, int k,
                                             int& fl, double* hits, int64_t hits_ld, int lane,
                                             const akb_fig::Map* F = nullptr, double* dfig = nullptr) {
@@ -689,16 +716,25 @@ __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& op
     if (kKind != kKindZFree) nz = div_pos(nz, sn, in);
     if (kFig && fig) {
         wave_flag(fout, AKB_FLAG_FIG_OUTSIDE << (4 * k), fl);
-        *dfig = *dfig + akb_fig::path_term(akb_fig::combine(fv, ftu, ftw, fout), akb_fig::dot_dn(l, m, n, nx, ny, nz));
+        if (!kSlope)
+            *dfig = *dfig + akb_fig::path_term(akb_fig::combine(fv, ftu, ftw, fout), akb_fig::dot_dn(l, m, n, nx, ny, nz));
+        if (kSlope) {
+            const double dn = akb_fig::dot_dn(l, m, n, nx, ny, nz);
+            if (kOPL) *dfig = *dfig + akb_fig::path_term(akb_fig::combine(fv, ftu, ftw, fout), dn);
+            double hu, hw;
+            akb_fig::gradient(fv, ftu, ftw, *F, fout, hu, hw);
+            akb_fig::deflect(nx, ny, nz, dn, *F, hu, hw, fout);
+        }
     }
-    // reflection
+    // reflection (a deflected normal: the general form)
+    const bool defl = kSlope && fig;  // wave-uniform
     double rx, ry, rz;
-    if (kKind == kKindYFree) {
+    if (kKind == kKindYFree && !defl) {
         const double A2 = 2.0 * (l * nx + n * nz);
         rx = l - A2 * nx;
         ry = m;
         rz = n - A2 * nz;
-    } else if (kKind == kKindZFree) {
+    } else if (kKind == kKindZFree && !defl) {
         const double A2 = 2.0 * (l * nx + m * ny);
         rx = l - A2 * nx;
         ry = m - A2 * ny;
@@ -762,8 +798,9 @@ __device__ __forceinline__ void ray_tables(const ChainArgs& a, int64_t i, uint32
 // tests' masks were what overflowed the scalar registers into VGPR lanes).
 // kFig: the mirrors' figure terms (fg: the launch's maps), summed in mirror order into d_fig and
 // added to the path behind the perturbation, opl = (opl + d_pert) + d_fig; never with kLean.
+// kSlope: the mapped mirrors deflect (mirror_step's kSlope); without kOPL no path term is formed.
 template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false, bool kFig = false, class Post = NoHook>
+          bool kFixed = false, bool kFig = false, class Post = NoHook, bool kSlope = false>
 __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, int t, uint32_t iv, uint32_t ih,
                                               double th, double tv, int& fl, double (&qv)[5], Post post = Post(),
                                               const FigArgs* fg = nullptr) {
@@ -810,13 +847,13 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
             k0 = 1;
         } else {
             if (a.kind[0] == kKindYFree)
-                mirror_step<kKindYFree, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                mirror_step<kKindYFree, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
                                                                              kFig ? &fg->m[0] : nullptr, &dfig);
             else if (a.kind[0] == kKindZFree)
-                mirror_step<kKindZFree, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                mirror_step<kKindZFree, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
                                                                              kFig ? &fg->m[0] : nullptr, &dfig);
             else
-                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true, false, kFig>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
+                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
                                                                              kFig ? &fg->m[0] : nullptr, &dfig);
             k0 = 1;
         }
@@ -827,13 +864,13 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
 #pragma unroll 1
     for (int k = k0; k < kend; ++k) {
         if (a.kind[k] == kKindYFree)  // wave-uniform branch
-            mirror_step<kKindYFree, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+            mirror_step<kKindYFree, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
                                                                         kFig ? &fg->m[k] : nullptr, &dfig);
         else if (a.kind[k] == kKindZFree)
-            mirror_step<kKindZFree, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+            mirror_step<kKindZFree, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
                                                                         kFig ? &fg->m[k] : nullptr, &dfig);
         else
-            mirror_step<kKindGeneral, kOPL, kHits, kGrid, false, false, kFig>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
+            mirror_step<kKindGeneral, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
                                                                         kFig ? &fg->m[k] : nullptr, &dfig);
     }
     if (kLean && kend >= k0) {  // the last mirror: its flags only
@@ -858,7 +895,7 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
     if (kLean) return;
     const uint32_t off = (uint32_t)t << 3;
     if (kOPL && (kFixed || a.opl)) st_off(a.opl + i0, off, opl);
-    if (kFig && fg->out) st_off(fg->out + i0, off, dfig);
+    if (kFig && kOPL && fg->out) st_off(fg->out + i0, off, dfig);
     if (!kLean && (kFixed || a.last_hit)) {
         double* o = a.last_hit + i0;
         st_off(o, off, p);
@@ -900,14 +937,14 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
 
 // the same, loading its own table entries (the unpipelined kernels)
 template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false, bool kFig = false>
+          bool kFixed = false, bool kFig = false, bool kSlope = false>
 __device__ __forceinline__ void chain_ray(const ChainArgs& a, int64_t i0, int t, int& fl, double (&qv)[5],
                                           const FigArgs* fg = nullptr) {
     uint32_t iv = 0, ih = 0;
     double th = 0.0, tv = 0.0;
     if (kGrid) ray_tables(a, i0 + t, iv, ih, th, tv);
-    chain_ray_tab<kGrid, kOPL, kNeedQ, kHits, kLean, kPointSrc, kFixed, kFig>(a, i0, t, iv, ih, th, tv, fl, qv, NoHook(),
-                                                                            fg);
+    chain_ray_tab<kGrid, kOPL, kNeedQ, kHits, kLean, kPointSrc, kFixed, kFig, NoHook, kSlope>(a, i0, t, iv, ih, th, tv, fl,
+                                                                                             qv, NoHook(), fg);
 }
 
 template <bool kGrid, bool kOPL, int kWaves, bool kHits = false, bool kPointSrc = false>
@@ -921,15 +958,16 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain(ChainArgs a) {
     if (fl) atomicOr(a.flags, fl);
 }
 
-// k_chain with the mirrors' figure terms (always with the OPL row)
-template <bool kGrid, bool kHits>
+// k_chain with the mirrors' figure terms (always with the OPL row); kSlope: the mapped mirrors
+// deflect, with or without the OPL row
+template <bool kGrid, bool kHits, bool kSlope = false, bool kOPL = true>
 __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_fig(ChainArgsFig a) {
     stage_copy(a);
     int fl = 0;
     double qv[5];
     const int t = threadIdx.x;
     for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
-        if (i0 + t < a.n) chain_ray<kGrid, true, false, kHits, false, false, false, true>(a, i0, t, fl, qv, &a.fig);
+        if (i0 + t < a.n) chain_ray<kGrid, kOPL, false, kHits, false, false, false, true, kSlope>(a, i0, t, fl, qv, &a.fig);
     if (fl) atomicOr(a.flags, fl);
 }
 
@@ -1051,7 +1089,7 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_sink(ChainArgs a) {
 
 // k_chain_sink with the mirrors' figure terms; kFixed (grid rays from the point source, RayWave's
 // pass-2 output set) as there
-template <bool kGrid, bool kFixed>
+template <bool kGrid, bool kFixed, bool kSlope = false>
 __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_sink_fig(ChainArgsFig a) {
     stage_copy(a);
     __shared__ LeafLds<5> L;
@@ -1061,7 +1099,7 @@ __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_sink_fig(ChainArgsF
     for (int64_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
         const bool valid = seg * kLeafSeg + t < a.n;
         double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (valid) chain_ray<kGrid, true, true, false, false, kFixed, kFixed, true>(a, seg * kLeafSeg, t, fl, qv, &a.fig);
+        if (valid) chain_ray<kGrid, true, true, false, false, kFixed, kFixed, true, kSlope>(a, seg * kLeafSeg, t, fl, qv, &a.fig);
         leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);
     }
     if (fl) atomicOr(a.flags, fl);
@@ -1079,6 +1117,19 @@ __global__ void __launch_bounds__(kBlock) k_chain_batch(const ChainArgs* __restr
     const int t = threadIdx.x;
     for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
         if (i0 + t < a.n) chain_ray<true, kOPL, false, kHits, false, false>(a, i0, t, fl, qv);
+    if (fl) atomicOr(a.flags, fl);
+}
+
+// k_chain_batch for systems whose mapped mirrors deflect (fig_slope): the per-system arguments, maps
+// included, from device memory at the wave-uniform address
+template <bool kOPL, bool kHits>
+__global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_batch_fig(const ChainArgsFig* __restrict__ A) {
+    const ChainArgsFig& a = A[blockIdx.y];
+    int fl = 0;
+    double qv[5];
+    const int t = threadIdx.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
+        if (i0 + t < a.n) chain_ray<true, kOPL, false, kHits, false, false, false, true, true>(a, i0, t, fl, qv, &a.fig);
     if (fl) atomicOr(a.flags, fl);
 }
 
@@ -2007,11 +2058,17 @@ static bool desc_has_fig(const akb_chain_desc* d) {
     return false;
 }
 
-// the entry points with no figure plumbing refuse such a descriptor before they launch anything
+// the entry points with no figure plumbing refuse such a descriptor before they launch anything;
+// fig_slope is refused by itself too: the wavefront modes keep the thin screen
 #define AKB_REFUSE_FIG(d, who)                                                                          \
     do {                                                                                                \
         if ((d) != nullptr && desc_has_fig(d)) {                                                        \
             set_error(who ": figure maps (fig / fig_out) are implemented by akb_trace_chain_f64 only"); \
+            return AKB_E_ARG;                                                                           \
+        }                                                                                               \
+        if ((d) != nullptr && (d)->fig_slope != 0) {                                                    \
+            set_error(who ": figure maps deflect the rays (fig_slope) in akb_trace_chain_f64 and "      \
+                          "akb_trace_chain_batch_f64 only");                                            \
             return AKB_E_ARG;                                                                           \
         }                                                                                               \
     } while (0)
@@ -2063,10 +2120,24 @@ int akb_figure_opl_f64(const akb_figure_map* map, const double coeffs[10], const
     return launch_status("k_figure_opl");
 }
 
-// the chain with figure maps: its own kernels (k_chain_fig / k_chain_sink_fig), the plain chain's grids
-static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStream_t s) {
-    AKB_REQUIRE(d->opl != nullptr, "figure maps add to the optical path: the descriptor needs opl");
-    ChainArgsFig f{};
+int akb_figure_normal_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                          const double* dir, int64_t dir_ld, int64_t n, double* normal_out, int64_t normal_ld,
+                          int32_t* flags, void* stream) {
+    clear_error();
+    AKB_REQUIRE(map && coeffs && hit && dir && normal_out && flags, "null pointer");
+    AKB_REQUIRE(n >= 0 && hit_ld >= n && dir_ld >= n && normal_ld >= n, "bad sizes");
+    akb_fig::Map M;
+    const int st = fig_map_from(map, M);
+    if (st != AKB_OK) return st;
+    if (n == 0) return AKB_OK;
+    k_figure_normal<<<grid_for(n, 1, kStreamGridCap), kBlock, 0, (hipStream_t)stream>>>(
+        M, quadric_from(coeffs), v3in(hit, hit_ld, 1), v3in(dir, dir_ld, 1), n, V3Out{normal_out, normal_ld}, flags);
+    return launch_status("k_figure_normal");
+}
+
+// the kernel arguments with the descriptor's maps
+static int fig_args_from(const akb_chain_desc* d, const ChainArgs& a, ChainArgsFig& f) {
+    f = ChainArgsFig{};
     static_cast<ChainArgs&>(f) = a;
     for (int k = 0; k < AKB_MAX_MIRRORS; ++k) {
         if (!d->fig[k].table) continue;
@@ -2075,6 +2146,24 @@ static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStre
         if (st != AKB_OK) return st;
     }
     f.fig.out = d->fig_out;
+    return AKB_OK;
+}
+
+}  // extern "C" (templates have C++ linkage)
+
+// k_chain_fig with or without the OPL row; without kSlope the row is always there (both branches name
+// the same instantiation)
+template <bool kGrid, bool kHits, bool kSlope>
+static void launch_k_chain_fig(bool opl, unsigned g, hipStream_t s, const ChainArgsFig& f) {
+    if (opl)
+        k_chain_fig<kGrid, kHits, kSlope, true><<<g, kBlock, 0, s>>>(f);
+    else
+        k_chain_fig<kGrid, kHits, kSlope, !kSlope><<<g, kBlock, 0, s>>>(f);
+}
+
+// the dispatch over the figure kernels' instantiations, the plain chain's grids
+template <bool kSlope>
+static int launch_fig_kernels(const akb_chain_desc* d, const ChainArgs& a, const ChainArgsFig& f, hipStream_t s) {
     const bool grid = d->dir == nullptr;
     if (d->sink.nq > 0) {
         const int64_t nseg = (d->n_rays + kLeafSeg - 1) / kLeafSeg;
@@ -2083,23 +2172,39 @@ static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStre
         const bool fixed = grid && a.org == nullptr && a.last_hit && a.dir_out && !a.det_out && !a.atan_h &&
                            !a.atan_v && !a.samp_h && !a.samp_v && !a.hits;
         if (fixed)
-            k_chain_sink_fig<true, true><<<gs, kBlock, 0, s>>>(f);
+            k_chain_sink_fig<true, true, kSlope><<<gs, kBlock, 0, s>>>(f);
         else if (grid)
-            k_chain_sink_fig<true, false><<<gs, kBlock, 0, s>>>(f);
+            k_chain_sink_fig<true, false, kSlope><<<gs, kBlock, 0, s>>>(f);
         else
-            k_chain_sink_fig<false, false><<<gs, kBlock, 0, s>>>(f);
+            k_chain_sink_fig<false, false, kSlope><<<gs, kBlock, 0, s>>>(f);
         return launch_status("k_chain_sink_fig");
     }
     const unsigned g = grid_for(d->n_rays, 1, kChainGridCap);
+    const bool opl = d->opl != nullptr;
     if (grid && a.hits)
-        k_chain_fig<true, true><<<g, kBlock, 0, s>>>(f);
+        launch_k_chain_fig<true, true, kSlope>(opl, g, s, f);
     else if (grid)
-        k_chain_fig<true, false><<<g, kBlock, 0, s>>>(f);
+        launch_k_chain_fig<true, false, kSlope>(opl, g, s, f);
     else if (a.hits)
-        k_chain_fig<false, true><<<g, kBlock, 0, s>>>(f);
+        launch_k_chain_fig<false, true, kSlope>(opl, g, s, f);
     else
-        k_chain_fig<false, false><<<g, kBlock, 0, s>>>(f);
+        launch_k_chain_fig<false, false, kSlope>(opl, g, s, f);
     return launch_status("k_chain_fig");
+}
+
+extern "C" {
+
+// the chain with figure maps: its own kernels (k_chain_fig / k_chain_sink_fig), the plain chain's grids
+static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStream_t s) {
+    const bool slope = d->fig_slope != 0;
+    // the path term needs the OPL row; maps that only deflect (fig_slope) do without it
+    AKB_REQUIRE(d->opl != nullptr || (slope && d->fig_out == nullptr),
+                "figure maps add to the optical path: the descriptor needs opl (or fig_slope and no fig_out)");
+    AKB_REQUIRE(d->opl != nullptr || d->sink.nq == 0, "the chain sink with figure maps needs opl");
+    ChainArgsFig f;
+    const int fst = fig_args_from(d, a, f);
+    if (fst != AKB_OK) return fst;
+    return slope ? launch_fig_kernels<true>(d, a, f, s) : launch_fig_kernels<false>(d, a, f, s);
 }
 
 int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
@@ -2400,14 +2505,27 @@ int akb_tilt_opd_dev_f64(const double* d_params, const double det1_ghij[4], cons
 int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stream) {
     clear_error();
     AKB_REQUIRE(descs != nullptr && n_sys > 0 && n_sys <= 65535, "need 1..65535 descriptors");
-    for (int s = 0; s < n_sys; ++s) AKB_REFUSE_FIG(descs + s, "akb_trace_chain_batch_f64");
+    // maps are taken only where they deflect (fig_slope): the batch has no path-term plumbing of its
+    // own beyond the chain's, and a map that would silently not deflect a spot mode is refused
+    bool any_fig = false;
+    for (int s = 0; s < n_sys; ++s) {
+        if (!desc_has_fig(descs + s)) continue;
+        if (descs[s].fig_slope == 0) {
+            set_error("akb_trace_chain_batch_f64: figure maps (fig / fig_out) are taken with fig_slope set only");
+            return AKB_E_ARG;
+        }
+        any_fig = true;
+    }
     std::vector<ChainArgs> args((size_t)n_sys);
+    std::vector<ChainArgsFig> fargs(any_fig ? (size_t)n_sys : 0);
     int64_t nmax = 0;
     for (int s = 0; s < n_sys; ++s) {
         const akb_chain_desc* d = descs + s;
         bool empty = false;
         const int st = chain_args_from(d, args[s], empty);
         if (st != AKB_OK) return st;
+        if (desc_has_fig(d))
+            AKB_REQUIRE(d->opl != nullptr || d->fig_out == nullptr, "fig_out needs the opl row");
         AKB_REQUIRE(d->dir == nullptr, "batched systems take grid rays (tan_h / tan_v)");
         AKB_REQUIRE(d->sink.nq == 0 && d->samp_h == nullptr && d->samp_v == nullptr && d->copy_n == 0,
                     "batched systems have no sink, resample picks or staging copy");
@@ -2416,16 +2534,36 @@ int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stre
                     "every system of a batch asks for the same opl / hits rows");
         if (empty) args[s].n = 0;
         if (args[s].n > nmax) nmax = args[s].n;
+        if (any_fig) {
+            const int fst = fig_args_from(d, args[s], fargs[s]);
+            if (fst != AKB_OK) return fst;
+        }
     }
     if (nmax == 0) return AKB_OK;
     hipStream_t s = (hipStream_t)stream;
     void* d_args = nullptr;
-    int st = stage_args(args.data(), sizeof(ChainArgs) * args.size(), s, &d_args);
-    if (st != AKB_OK) return st;
     const unsigned gx = grid_for(nmax, 1, 4096);
     const dim3 grid(gx, (unsigned)n_sys);
-    const ChainArgs* A = (const ChainArgs*)d_args;
     const bool opl = descs[0].opl != nullptr, hits = descs[0].hits != nullptr;
+    if (any_fig) {  // a system without maps runs the same kernel with every table NULL
+        int st = stage_args(fargs.data(), sizeof(ChainArgsFig) * fargs.size(), s, &d_args);
+        if (st != AKB_OK) return st;
+        const ChainArgsFig* A = (const ChainArgsFig*)d_args;
+        if (opl && hits)
+            k_chain_batch_fig<true, true><<<grid, kBlock, 0, s>>>(A);
+        else if (opl)
+            k_chain_batch_fig<true, false><<<grid, kBlock, 0, s>>>(A);
+        else if (hits)
+            k_chain_batch_fig<false, true><<<grid, kBlock, 0, s>>>(A);
+        else
+            k_chain_batch_fig<false, false><<<grid, kBlock, 0, s>>>(A);
+        st = launch_status("k_chain_batch_fig");
+        AKB_HIP_CHECK(hipFreeAsync(d_args, s));
+        return st;
+    }
+    int st = stage_args(args.data(), sizeof(ChainArgs) * args.size(), s, &d_args);
+    if (st != AKB_OK) return st;
+    const ChainArgs* A = (const ChainArgs*)d_args;
     if (opl && hits)
         k_chain_batch<true, true><<<grid, kBlock, 0, s>>>(A);
     else if (opl)

@@ -16,6 +16,11 @@ give the same bits.
 
 A hit outside the map contributes 0 and raises the mirror's AKB_FLAG_FIG_OUTSIDE bit; RayWave turns
 that into an AKBError naming the mirror.
+
+The ray-spot modes (the batched 'test' trace, auto_focus_NA, calc_FoC; trace_chain(figure_slope=True))
+also let the map deflect the ray: the reflection takes N' = (N - sigma g) / ||N - sigma g|| with
+g = dh/du e_u + dh/dw e_w the map's gradient and sigma N the normal turned towards the incoming beam
+(DESIGN 7.5). stage_normals is that trace stage by stage. The wavefront modes keep the thin screen.
 """
 import numpy as np
 
@@ -140,11 +145,27 @@ def _centre_ray(geometry):
     return out
 
 
+class _GeometryView:
+    """mirrors, source and the two angle ranges of what geometry.build_akb / build_kb return"""
+
+    def __init__(self, built):
+        from . import geometry as G
+        from .wavefront import AngleRange
+        self.mirrors = G.mirrors_of(built)
+        self.source = [float(x) for x in built["source"]]
+        self.angle_h = AngleRange(**built["angle_h"])
+        self.angle_v = AngleRange(**built["angle_v"])
+
+
 def mirror_frames(geometry):
     """One frame per mirror from the launch grid's centre ray: origin = its hit, e_u = the incoming
     direction projected onto the tangent plane and normalised, e_w = n x e_u with n the unit normal
     turned towards the incoming beam - the frame in which a fabricator's length profile is
-    measured. Returns a list of dicts (origin, e_u, e_w, normal, grazing = the centre ray's |d . n|)."""
+    measured. geometry: a SystemGeometry, or the dict geometry.build_akb / build_kb return (only the
+    mirrors, the source and the two angle ranges are read). Returns a list of dicts (origin, e_u, e_w,
+    normal, grazing = the centre ray's |d . n|)."""
+    if isinstance(geometry, dict):
+        geometry = _GeometryView(geometry)
     frames = []
     for hit, d, N in _centre_ray(geometry):
         n = -N if d @ N > 0 else N
@@ -215,3 +236,66 @@ def stage_terms(mirrors, figure, hits, dirs0, prims=None, flags_out=None):
         if k + 1 < len(mirrors):
             ray = prims.reflect_ray(ray, prims.norm_vector(m.coeffs, p))
     return out, word
+
+
+def figure_normal(fm, coeffs, hit, ray):
+    """One mirror's deflected unit normals (akb_figure_normal_f64) from hits and unit incoming
+    directions, (3, n) device tensors: ((3, n) normals, the kernel's flag word)."""
+    import torch
+
+    from . import device as D
+    n = hit.shape[1]
+    hit, ray = hit.contiguous(), ray.contiguous()
+    out = torch.empty((3, n), dtype=D.F64, device=hit.device)
+    fl = torch.zeros(1, dtype=torch.int32, device=hit.device)
+    _lib.check(_lib.lib().akb_figure_normal_f64(fm.desc(hit.device), D.host_f64(coeffs), D.ptr(hit), n, D.ptr(ray), n, n,
+                                                D.ptr(out), n, D.ptr(fl), D.stream_handle()))
+    return out, int(fl.item())
+
+
+def stage_normals(mirrors, figure, dirs, src, with_segments=False, prims=None, with_terms=False):
+    """trace.staged_chain with the mapped mirrors deflecting: per mirror the intersection, then the
+    deflected normal (akb_figure_normal_f64; norm_vector for a mirror without a map), then reflect_ray -
+    what the fused chain with figure_slope gives, bit for bit, and the path a flagged trace takes (the
+    primitives apply the reference's all-NaN / passthrough rules). dirs, src: (3, n) device tensors;
+    prims as in stage_terms. Returns (hits, exit directions, segments, flag word with mirror k's
+    AKB_FLAG_FIG_OUTSIDE at 4k); with_terms appends the path terms' sum in mirror order (stage_terms'
+    value on the deflected path: akb_figure_opl_f64 with each mirror's actual incoming directions)."""
+    import torch
+
+    from . import device as D
+    from . import primitives as P
+    prims = prims if prims is not None else P
+    hits, segs = [], []
+    ray, org = dirs, src
+    word = 0
+    terms, started = None, False
+    if with_terms:
+        terms = torch.zeros(dirs.shape[1], dtype=D.F64, device=dirs.device)
+    for k, m in enumerate(mirrors):
+        p = prims.mirr_ray_intersection(m.coeffs, ray, org, negative=m.negative)
+        if with_segments:
+            segs.append(prims.segment_length(org, p))
+        f = figure[k] if figure is not None else None
+        nrm = None
+        if f is not None and with_terms:
+            n = p.shape[1]
+            pc, rc = p.contiguous(), ray.contiguous()
+            tfl = torch.zeros(1, dtype=torch.int32, device=p.device)
+            _lib.check(_lib.lib().akb_figure_opl_f64(f.desc(p.device), D.host_f64(m.coeffs), D.ptr(pc), n, 1, D.ptr(rc),
+                                                     n, 1, n, D.ptr(terms), int(started), D.ptr(tfl), D.stream_handle()))
+            started = True
+        if f is not None:
+            nrm, fl = figure_normal(f, m.coeffs, p, ray)
+            if fl & _lib.FLAG_FIG_OUTSIDE:
+                word |= _lib.FLAG_FIG_OUTSIDE << (4 * k)
+            if fl & _lib.FLAG_ZERO_NORMAL:  # the reference's passthrough rule, undeflected
+                nrm = None
+        if nrm is None:
+            nrm = prims.norm_vector(m.coeffs, p)
+        ray = prims.reflect_ray(ray, nrm)
+        org = p
+        hits.append(p)
+    if with_terms:
+        return hits, ray, segs, word, terms
+    return hits, ray, segs, word

@@ -69,7 +69,7 @@ class ChainLaunch:
 
     def __init__(self, mirrors, *, tan_h=None, tan_v=None, row0=0, n_rays=None, dirs=None, src=(0.0, 0.0, 0.0),
                  det_ghij=None, want=("last_hit", "dir_out"), samples=None, out=None, sink=None, flags=None,
-                 samples_buf=None, pert=None, ray0=None, precision="fp64", figure=None):
+                 samples_buf=None, pert=None, ray0=None, precision="fp64", figure=None, figure_slope=False):
         from .figure import check_figure
         if precision not in ("fp64", "dd"):
             raise ValueError('precision must be "fp64" or "dd"')
@@ -79,6 +79,9 @@ class ChainLaunch:
         if precision == "dd" and (figure is not None or "fig_opl" in want):
             raise ValueError('the double-double chain (precision="dd") has no fused figure maps: add the terms '
                              'with figure.stage_terms from its hits')
+        if precision == "dd" and figure_slope:
+            raise ValueError('the double-double chain (precision="dd") does not deflect at figure maps '
+                             '(figure_slope): the wavefront modes keep the thin screen')
         self.precision = precision
         dev = D.device()
         desc = _lib.ChainDesc()
@@ -170,9 +173,12 @@ class ChainLaunch:
                 raise ValueError("perturbation tables must be (terms, n_h) and (terms, n_v)")
             desc.pert_h, desc.pert_v, desc.pert_terms = D.ptr(ph), D.ptr(pv), int(ph.shape[0])
             self.keep += [ph, pv]
+        if figure_slope:
+            desc.fig_slope = 1
         if figure is not None or "fig_opl" in want:
-            if "opl" not in want:
-                raise ValueError("figure maps add to the optical path: want must contain 'opl'")
+            if "opl" not in want and not (figure_slope and "fig_opl" not in want):
+                raise ValueError("figure maps add to the optical path: want must contain 'opl' (maps that only "
+                                 "deflect, figure_slope=True, do without it)")
             for k, f in enumerate(figure or ()):
                 if f is not None:
                     self.keep.append(f.fill(desc.fig[k], dev))
@@ -201,6 +207,10 @@ def trace_chain(mirrors, *, stream=None, **kw):
     figure: optional list with one figure.FigureMap or None per mirror: each mapped mirror adds
         -2 h |d . N| to the ray's opl (csrc/akb_figure.h); "fig_opl" in want returns the terms' sum.
         A hit outside a map contributes 0 and raises FLAG_FIG_OUTSIDE << 4k in the flag word.
+    figure_slope: True makes the mapped mirrors deflect the ray as well (slope error, for the spot
+        modes): the reflection takes the normal turned by the map's gradient (akb_figure_normal_f64's,
+        bit for bit figure.stage_normals' staged composition); the path term keeps the quadric's normal,
+        and 'opl' is no longer required (without it no path term is formed). Not with precision="dd".
     samples: (h_begin, h_end, v_col) flat-index range / column whose exit slopes to record.
     flags / samples_buf: optional caller-owned int32 flag word and float64 pick buffer (RayWave
         places the flag words right after the picks so one copy brings both to the host).

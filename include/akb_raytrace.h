@@ -25,6 +25,9 @@
  *   akb_reflect_dd_f64   reflect_ray, option_mpmath branch             AKB_raytrace_20250312.py:474-500, :510-552
  *   akb_figure_opl_f64   (no reference call: the measured figure error that compareCSV.py /
  *                        surfacedetailAKB.py plot, fed back into the optical path; csrc/akb_figure.h)
+ *   akb_figure_normal_f64 (no reference call: the same map's slope turning the normal the reflection
+ *                        uses - slope error in the ray-spot modes; akb_chain_desc.fig_slope fuses it
+ *                        into akb_trace_chain_f64 and akb_trace_chain_batch_f64)
  *   akb_trace_chain_f64  the pass-1 / pass-2 mirror chains of plot_result_debug
  *                        AKB_raytrace_20250312.py:2694-2717 (ray grid), :2770-2845 (pass 1),
  *                        :2881-2905 (pass 2 + OPL segments); KB_debug :10952-10997
@@ -143,6 +146,20 @@ int akb_figure_opl_f64(const akb_figure_map* map, const double coeffs[10], const
                        int64_t hit_inc, const double* dir, int64_t dir_ld, int64_t dir_inc, int64_t n, double* out,
                        int accumulate, int32_t* flags, void* stream);
 
+/* One mirror's deflected unit normal for n rays from materialised hit points (3, hit_ld) and unit
+ * incoming directions (3, dir_ld): with N the quadric's unit normal at the hit (akb_normal_f64's
+ * expressions), (hu, hw) the gradient of the map's Catmull-Rom interpolant there (from the sixteen
+ * samples and two fractions of the height, no further load), sigma = (dir . N > 0) ? -1 : 1 and
+ * g = hu e_u + hw e_w,
+ *     N' = (N - sigma g) / ||N - sigma g||
+ * (positive h is a bump towards the incoming beam). normal_out (3, normal_ld) receives N', or N itself
+ * for a hit outside the map, which ORs AKB_FLAG_FIG_OUTSIDE into *flags; a NaN hit gives a NaN normal
+ * and no flag; AKB_FLAG_ZERO_NORMAL as akb_normal_f64. intersection -> this -> akb_reflect_f64 is the
+ * staged composition the fused kernels with fig_slope equal bit for bit. */
+int akb_figure_normal_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                          const double* dir, int64_t dir_ld, int64_t n, double* normal_out, int64_t normal_ld,
+                          int32_t* flags, void* stream);
+
 /* normalize_vector: out = v / ||v|| ; ORs AKB_FLAG_ZERO_DIR if any ||v|| == 0 (caller keeps v). */
 int akb_normalize_f64(const double* v, int64_t v_ld, int64_t v_inc, int64_t n, double* out,
                       int64_t out_ld, int32_t* flags, void* stream);
@@ -249,9 +266,17 @@ typedef struct akb_chain_desc {
      * path, opl = (opl + perturbation) + d_fig with d_fig = ((0 + delta_0) + delta_1) + ... in mirror
      * order over the mirrors that have a map; fig_out (optional, (n)) receives d_fig. A hit outside
      * mirror k's map contributes 0 and raises AKB_FLAG_FIG_OUTSIDE << 4k. akb_trace_chain_f64 only:
-     * every other entry point that takes a descriptor refuses one with a map or fig_out (AKB_E_ARG) */
+     * every other entry point that takes a descriptor refuses one with a map or fig_out (AKB_E_ARG;
+     * akb_trace_chain_batch_f64 takes maps with fig_slope set) */
     akb_figure_map fig[AKB_MAX_MIRRORS];
     double* fig_out;
+    /* fig_slope != 0: the mapped mirrors also deflect the ray - the reflection at mirror k takes
+     * akb_figure_normal_f64's N' in place of N (bit for bit the staged composition); the path term keeps
+     * the quadric's own N, and maps without opl become legal (no path term is formed then; fig_out
+     * still needs opl). A hit outside the map reflects about N and raises the flag as above.
+     * akb_trace_chain_f64 and akb_trace_chain_batch_f64 only; the wavefront entry points (double-double
+     * chain, picks, fused pass 1 + tilt) refuse it: AKB_E_ARG. */
+    int32_t fig_slope;
 } akb_chain_desc;
 
 int akb_trace_chain_f64(const akb_chain_desc* desc, void* stream);
@@ -263,7 +288,7 @@ int akb_trace_chain_f64(const akb_chain_desc* desc, void* stream);
  * stage entry points composed in that order. Same descriptor: grid or explicit directions, ray0 /
  * n_rays, constant or per-ray origins; outputs hits, last_hit, dir_out, det_out, opl, atan_h / v,
  * samp_h / v, flags (mirror k's bits shifted by 4k; a missed ray's columns are NaN from that mirror
- * on). sink, pert_*, copy_* and fig / fig_out are not implemented: AKB_E_ARG. */
+ * on). sink, pert_*, copy_*, fig / fig_out and fig_slope are not implemented: AKB_E_ARG. */
 int akb_trace_chain_dd_f64(const akb_chain_desc* desc, void* stream);
 /* sizeof(akb_chain_desc), for bindings to check their struct layout */
 int64_t akb_chain_desc_size(void);
@@ -340,7 +365,9 @@ int akb_chain_tilt_opd_f64(const akb_chain_desc* d, const double* d_params, cons
 /* S independent systems in one launch (auto_focus_NA / calc_FoC trace many small systems, ref
  * AKB_raytrace_20250312.py:12776-12786, :13780-13784): descs[s] is an akb_trace_chain_f64 descriptor
  * (host array) with grid rays, no sink, resample picks or staging copy, and every system asking for
- * the same opl / hits rows. Each system's outputs and flag word are its own. */
+ * the same opl / hits rows. Each system's outputs and flag word are its own. Figure maps are taken
+ * when every descriptor that has one sets fig_slope (the spot modes: the maps deflect; with opl they
+ * add their path terms as in akb_trace_chain_f64); a map with fig_slope = 0 is refused, AKB_E_ARG. */
 int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stream);
 
 /* The focus evaluation of plot_result_debug's 'test' mode and auto_focus_NA's spot sizes (ref
