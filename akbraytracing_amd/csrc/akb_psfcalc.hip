@@ -1061,7 +1061,9 @@ __global__ void __launch_bounds__(kPostThreads) k_pupil_post(PostArgs a) {
     moments(5, sys, 0.0, 2, mu, acc);
     const double thr = a.sigma * sqrt(acc[0] / n1);
     moments(3, sys, thr, 0, 0.0, acc);
-    if (tid == 0 && acc[20] < 3) sflag |= 1;
+    // (after a singular first system no coefficient is finite and the filter keeps no point: the host
+    // chain has raised numpy's LinAlgError by then, so that empty set is not "too few points")
+    if (tid == 0 && acc[20] < 3 && !(sflag & 2)) sflag |= 1;
     normal_solve(acc, std::integral_constant<int, 3>{}, 8);  // p2 = sys[8..11)
     if (tid == 0) a.clocks[3] = wall_clock64();
     // corrected = (map - nanmean) - plane, and rotate_with_nan's NaN split of it; psf_calc's rotation

@@ -204,7 +204,9 @@ def pupil_post(m, sigma_threshold=3, out=None, stream=None):
     m: (ny, nx) device map, ny * nx <= 65536. out: optional dict of preallocated buffers.
     Returns dict(corrected, rotated, opd, params) of device tensors; params[17] holds error flags
     (bit 0: too few points for the fits, bit 1: a singular normal system), read by the caller when
-    it can wait (pupil_post_check); params[18], [19]: the input map's nanmin and nanmax."""
+    it can wait (pupil_post_check); params[18], [19]: the input map's nanmin and nanmax.
+    A side of 2 makes the five-term fit exactly singular (the scaled index is +-1, its square the
+    constant term): flag bit 1, numpy's LinAlgError as from the host chain."""
     L = _lib.lib()
     m = _as_dev(m)
     ny, nx = int(m.shape[0]), int(m.shape[1])

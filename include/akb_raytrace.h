@@ -529,7 +529,10 @@ int akb_rotate_with_nan_f64(const double* m, int ny, int nx, const double rot[4]
  * both axes in LDS), the rotation. work: akb_pupil_post_work_bytes(ny, nx). d_params (20 doubles):
  * nanmean, finite count, the quadratic fit (5), the plane (3), the outlier threshold, rot, its
  * degrees, cos, sin, the rotation's offset (2), error flags (bit 0: too few points for curve_fit,
- * bit 1: a singular normal system), nanmin and nanmax of the input map. Replaces
+ * bit 1: a singular normal system - a side of 2 always is one: the scaled X or Y is +-1, its square
+ * the constant term, so the five-term fit is exactly singular; the flags are set in the host chain's
+ * order, so its first exception is the lowest bit set), nanmin and nanmax of the input map. ny and
+ * nx are at least 2. Replaces
  * pupilmap._plane_corrections + psfcalc.rotation_estimate / rotate_with_nan where a pipelined
  * caller cannot wait on the host. */
 int64_t akb_pupil_post_work_bytes(int ny, int nx);

@@ -67,6 +67,48 @@ def test_faithful_pipeline_vs_host_chain_and_reference(gpu, n):
     fp_.close()
 
 
+@pytest.mark.parametrize("size", [96, 160])
+def test_faithful_pipeline_at_other_pupil_sizes(gpu, size):
+    """FaithfulPupil(size=) off the bench's 128 (96: the post's fused prefilter on shorter lines; 160:
+    the map read from global memory, k_spline_block) on the 401^2 trace, against the host chain on
+    the same grid: equal axes and NaN masks, the map and PSF bars of
+    test_faithful_pipeline_vs_host_chain_and_reference (there is no golden PSF at these sizes)."""
+    from akbraytracing_amd import pupilmap as PM
+    from akbraytracing_amd.faithful import FaithfulPupil, image_axes_of
+    from akbraytracing_amd.psfcalc import psf_calc
+    n = 401
+    out = _trace(n)
+    d2 = out["detcenter2"]
+    y, z, w2 = d2[1], d2[2], out["wave2"]
+    fp_ = FaithfulPupil(n, n, size=size, slots=1)
+    r = fp_.run(y, z, w2)
+    fp_.slots[0]["last"].check()
+    torch.cuda.synchronize()
+    m, gh, gv, _ = PM.wave_pupil(d2, w2, n, n, grid_num_H=size, grid_num_V=size)
+    a = r["axes"].cpu().numpy()
+    assert np.array_equal(a[:size], gh[0]) and np.array_equal(a[size:2 * size], gv[:, 0])
+    want_c = m.cpu().numpy()
+    got_c = r["corrected"].cpu().numpy()
+    assert got_c.shape == (size, size)
+    rng_ = np.nanmax(want_c) - np.nanmin(want_c)
+    assert np.array_equal(np.isnan(got_c), np.isnan(want_c))
+    e_map = np.nanmax(np.abs(got_c - want_c)) / rng_
+    GH, GV = gh - np.mean(gh), gv - np.mean(gv)
+    host = psf_calc(m, GH, GV, 1e-2)
+    P = r["psf"][0].cpu().numpy()
+    assert P.shape == tuple(host["psf"].shape)
+    e_psf = float(np.max(np.abs(P - host["psf"].cpu().numpy())))
+    x_im, y_im = image_axes_of(r)
+    assert np.array_equal(x_im, host["x_im"]) and np.array_equal(y_im, host["y_im"])
+    ch, est = r["change"].cpu().numpy().view(np.float64)
+    print(f"n={n}, size={size}: pipelined vs host chain: corrected map {e_map:.2e} of the range, PSF {e_psf:.2e} of "
+          f"the peak; change at the target corners {ch:.2e}, value-error estimate {est / rng_:.2e} of the range")
+    assert est <= 1e-6 * rng_
+    assert e_map <= 3e-7
+    assert e_psf <= 1e-7
+    fp_.close()
+
+
 def test_faithful_pipeline_in_flight_runs_equal_one_at_a_time(gpu):
     """Runs begun several at a time (tickets finished in order, pocket jobs on worker threads) give
     each run's own PSF bit for bit, as when each is begun and finished alone."""
