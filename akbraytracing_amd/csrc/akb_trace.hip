@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "akb_common.h"
@@ -610,11 +611,12 @@ struct Ray {
 // and the reflection takes the deflected normal N' in reflect_ray's general three-component form
 // whatever the mirror's kind (N' has all three components); the path term keeps the quadric's own
 // N and joins dfig only with kOPL. The instantiations without kSlope compile exactly as before.
-template <int kKind, bool kOPL, bool kHits, bool kUnitIn, bool kOrigin = false, bool kFlagsOnly = false,
-          bool kFig = false, bool kSlope = false>
+// M: the chain's mode (ChainMode below) - its kOPL, kHits, kFig and kSlope, and kUnitIn = M::kGrid.
+template <int kKind, class M, bool kOrigin, bool kFlagsOnly>
 __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& opl, int k,
                                             int& fl, double* hits, int64_t hits_ld, int lane,
-                                            const akb_fig::Map* F = nullptr, double* dfig = nullptr) {
+                                            const akb_fig::Map* F, double* dfig) {
+    constexpr bool kOPL = M::kOPL, kHits = M::kHits, kUnitIn = M::kGrid, kFig = M::kFig, kSlope = M::kSlope;
     const double l = R.l, m = R.m, n = R.n, p = R.p, q = R.q, r = R.r;
     double A, B, C;
     if (kKind == kKindYFree) {
@@ -761,13 +763,38 @@ __device__ __forceinline__ void mirror_step(const CMirror& Q, Ray& R, double& op
     R.r = z;
 }
 
-// One ray through the chain: ray i = i0 + t of a segment starting at the wave-uniform i0, t the
-// lane's position in it, so every per-ray output row is addressed as a scalar base plus a 32-bit
-// lane offset (no per-row 64-bit vector addresses held across the loop). Writes the requested
-// per-ray outputs and returns the sink quantities (arctan of the exit slopes and the detector hit)
-// in qv.
 struct NoHook {
     __device__ __forceinline__ void operator()() const {}
+};
+
+// What a chain kernel is compiled for: a mode is a type with these members, and a kernel names the
+// ones it turns on (chain_ray_tab's comment says what each means). Everything is off here.
+struct ChainMode {
+    static constexpr bool kGrid = false, kOPL = false, kNeedQ = false, kHits = false, kLean = false,
+                          kPointSrc = false, kFixed = false, kFig = false, kSlope = false;
+};
+// a launch's figure maps: none, the path term only, or maps that also deflect the rays
+enum FigMaps { kNoMaps, kMapsPath, kMapsDeflect };
+// the modes in use:
+// pass 1 of the fused kernel (k_chain_tilt)
+struct LeanPass1 : ChainMode {
+    static constexpr bool kGrid = true, kLean = true, kPointSrc = true;
+};
+// the kernels that write per-ray rows (k_chain, k_chain_batch and their _fig forms)
+template <bool kGridRays, bool kOplRow, bool kHitRows, bool kPointSource, FigMaps kMaps = kNoMaps>
+struct RowsMode : ChainMode {
+    static constexpr bool kGrid = kGridRays, kOPL = kOplRow, kHits = kHitRows, kPointSrc = kPointSource,
+                          kFig = kMaps != kNoMaps, kSlope = kMaps == kMapsDeflect;
+};
+// the kernels that also feed the five leaf sums (k_chain_sink, k_chain_sink_fig)
+template <bool kGridRays, bool kOplRow, bool kPointSource, FigMaps kMaps = kNoMaps>
+struct SinkMode : RowsMode<kGridRays, kOplRow, false, kPointSource, kMaps> {
+    static constexpr bool kNeedQ = true;
+};
+// pass 2 of RayWave: the sink kernel for grid rays from the point source with the fixed output set
+template <FigMaps kMaps = kNoMaps>
+struct FixedPass2 : SinkMode<true, true, true, kMaps> {
+    static constexpr bool kFixed = true;
 };
 
 // grid position and direction-table entries of flat ray i of a launch
@@ -777,6 +804,24 @@ __device__ __forceinline__ void ray_tables(const ChainArgs& a, int64_t i, uint32
     th = ld_off(a.tan_h, ih << 3);  // the tables hold fewer than 2^29 entries (checked on the host)
     tv = ld_off(a.tan_v, iv << 3);
 }
+
+// Mirror k of the chain by its kind (a wave-uniform branch), for chain_ray_tab's body. A macro: the
+// compiler optimises a function on its own before it inlines it, and with this switch in one every
+// chain kernel came out with other registers, spills and code (k_chain_tilt 5 instructions longer).
+// For the same reason each call forms the map's address itself: formed once ahead of the branch, the
+// kernels with maps compiled differently.
+#define AKB_MIRROR_BY_KIND(kOrigin, kFlagsOnly, k)                                                         \
+    do {                                                                                                   \
+        if (a.kind[k] == kKindYFree)                                                                       \
+            mirror_step<kKindYFree, M, kOrigin, kFlagsOnly>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,     \
+                                                            kFig ? &fg->m[k] : nullptr, &dfig);            \
+        else if (a.kind[k] == kKindZFree)                                                                  \
+            mirror_step<kKindZFree, M, kOrigin, kFlagsOnly>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,     \
+                                                            kFig ? &fg->m[k] : nullptr, &dfig);            \
+        else                                                                                               \
+            mirror_step<kKindGeneral, M, kOrigin, kFlagsOnly>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,   \
+                                                              kFig ? &fg->m[k] : nullptr, &dfig);          \
+    } while (0)
 
 // One ray through the chain: ray i = i0 + t of a segment starting at the wave-uniform i0, t the
 // lane's position in it, so every per-ray output row is addressed as a scalar base plus a 32-bit
@@ -789,21 +834,27 @@ __device__ __forceinline__ void ray_tables(const ChainArgs& a, int64_t i, uint32
 // (vmcnt), so loads issued after this segment's stores would make the next segment's first use
 // wait for those stores to reach memory; issued before them, they fly during the stores, the leaf
 // sums and (for the fused kernels) the next segment's mirror loop.
-// kLean: pass 1 of the fused kernel - only the flags leave the ray (the last mirror flags-only; no
+// M, the mode (a ChainMode; the named ones are above):
+// M::kGrid: the rays come from the launch's angle tables; otherwise from explicit directions (a.dir).
+// M::kOPL: the path length is formed (and written where a.opl is set).
+// M::kNeedQ: the sink quantities are always formed (the sink kernels).
+// M::kHits: the per-mirror hit rows are written.
+// M::kLean: pass 1 of the fused kernel - only the flags leave the ray (the last mirror flags-only; no
 // optional output rows, no out-of-line atan call).
-// kPointSrc: rays start at the constant source (no origin loads, which would have to be waited
+// M::kPointSrc: rays start at the constant source (no origin loads, which would have to be waited
 // for - with everything issued before them - ahead of the mirror loop).
-// kFixed: pass 2's output set, known at compile time - last hit, exit direction and OPL rows, no
+// M::kFixed: pass 2's output set, known at compile time - last hit, exit direction and OPL rows, no
 // detector / arctan rows, hits or picks - so none of the optional rows is tested per segment (their
 // tests' masks were what overflowed the scalar registers into VGPR lanes).
-// kFig: the mirrors' figure terms (fg: the launch's maps), summed in mirror order into d_fig and
+// M::kFig: the mirrors' figure terms (fg: the launch's maps), summed in mirror order into d_fig and
 // added to the path behind the perturbation, opl = (opl + d_pert) + d_fig; never with kLean.
-// kSlope: the mapped mirrors deflect (mirror_step's kSlope); without kOPL no path term is formed.
-template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false, bool kFig = false, class Post = NoHook, bool kSlope = false>
+// M::kSlope: the mapped mirrors deflect (mirror_step's kSlope); without kOPL no path term is formed.
+template <class M, class Post = NoHook>
 __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, int t, uint32_t iv, uint32_t ih,
                                               double th, double tv, int& fl, double (&qv)[5], Post post = Post(),
                                               const FigArgs* fg = nullptr) {
+    constexpr bool kGrid = M::kGrid, kOPL = M::kOPL, kNeedQ = M::kNeedQ, kHits = M::kHits, kLean = M::kLean,
+                   kPointSrc = M::kPointSrc, kFixed = M::kFixed, kFig = M::kFig;
     static_assert(!(kFig && kLean), "the lean pass 1 carries no figure maps");
     double dfig = 0.0;
     const int64_t i = i0 + t;
@@ -837,24 +888,11 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
     int k0 = 0;
     const int kend = kLean ? a.K - 1 : a.K;
     if (kGrid && a.origin0) {  // wave-uniform (grid rays: l > 0)
-        if (kLean && a.K == 1) {
-            if (a.kind[0] == kKindYFree)
-                mirror_step<kKindYFree, kOPL, kHits, kGrid, true, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
-            else if (a.kind[0] == kKindZFree)
-                mirror_step<kKindZFree, kOPL, kHits, kGrid, true, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
-            else
-                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true, true>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t);
+        if (kLean && a.K == 1) {  // also the last (kLean as the flag: no other mode has a flags-only step)
+            AKB_MIRROR_BY_KIND(true, kLean, 0);
             k0 = 1;
         } else {
-            if (a.kind[0] == kKindYFree)
-                mirror_step<kKindYFree, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
-                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
-            else if (a.kind[0] == kKindZFree)
-                mirror_step<kKindZFree, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
-                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
-            else
-                mirror_step<kKindGeneral, kOPL, kHits, kGrid, true, false, kFig, kSlope>(a.q[0], R, opl, 0, fl, hits, a.hits_ld, t,
-                                                                             kFig ? &fg->m[0] : nullptr, &dfig);
+            AKB_MIRROR_BY_KIND(true, false, 0);
             k0 = 1;
         }
     }
@@ -862,26 +900,9 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
     // with scalar loads (wave-uniform), keeping VGPR pressure and code size low (a fully unrolled
     // 4-mirror AKB kernel measured 12 % slower on MI355X)
 #pragma unroll 1
-    for (int k = k0; k < kend; ++k) {
-        if (a.kind[k] == kKindYFree)  // wave-uniform branch
-            mirror_step<kKindYFree, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
-                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
-        else if (a.kind[k] == kKindZFree)
-            mirror_step<kKindZFree, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
-                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
-        else
-            mirror_step<kKindGeneral, kOPL, kHits, kGrid, false, false, kFig, kSlope>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t,
-                                                                        kFig ? &fg->m[k] : nullptr, &dfig);
-    }
-    if (kLean && kend >= k0) {  // the last mirror: its flags only
-        const int k = kend;
-        if (a.kind[k] == kKindYFree)
-            mirror_step<kKindYFree, kOPL, kHits, kGrid, false, true>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
-        else if (a.kind[k] == kKindZFree)
-            mirror_step<kKindZFree, kOPL, kHits, kGrid, false, true>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
-        else
-            mirror_step<kKindGeneral, kOPL, kHits, kGrid, false, true>(a.q[k], R, opl, k, fl, hits, a.hits_ld, t);
-    }
+    for (int k = k0; k < kend; ++k) AKB_MIRROR_BY_KIND(false, false, k);
+    // the last mirror of a lean pass: its flags only
+    if (kLean && kend >= k0) AKB_MIRROR_BY_KIND(false, kLean, kend);
     const double l = R.l, m = R.m, nn = R.n, p = R.p, q = R.q, r = R.r;
     if (kOPL && kGrid && a.pert_h) {  // figure-error perturbation of the path (BASELINE config 5)
         double d = 0.0;
@@ -934,28 +955,60 @@ __device__ __forceinline__ void chain_ray_tab(const ChainArgs& a, int64_t i0, in
     if (a.samp_h && g >= a.sh_begin && g < a.sh_end) a.samp_h[g - a.sh_begin] = m / l;
     if (a.samp_v && kGrid && ih == a.sv_col) a.samp_v[iv] = nn / l;
 }
+#undef AKB_MIRROR_BY_KIND
 
 // the same, loading its own table entries (the unpipelined kernels)
-template <bool kGrid, bool kOPL, bool kNeedQ, bool kHits = false, bool kLean = false, bool kPointSrc = kLean,
-          bool kFixed = false, bool kFig = false, bool kSlope = false>
+template <class M>
 __device__ __forceinline__ void chain_ray(const ChainArgs& a, int64_t i0, int t, int& fl, double (&qv)[5],
                                           const FigArgs* fg = nullptr) {
     uint32_t iv = 0, ih = 0;
     double th = 0.0, tv = 0.0;
-    if (kGrid) ray_tables(a, i0 + t, iv, ih, th, tv);
-    chain_ray_tab<kGrid, kOPL, kNeedQ, kHits, kLean, kPointSrc, kFixed, kFig, NoHook, kSlope>(a, i0, t, iv, ih, th, tv, fl,
-                                                                                             qv, NoHook(), fg);
+    if (M::kGrid) ray_tables(a, i0 + t, iv, ih, th, tv);
+    chain_ray_tab<M>(a, i0, t, iv, ih, th, tv, fl, qv, NoHook(), fg);
 }
 
-template <bool kGrid, bool kOPL, int kWaves, bool kHits = false, bool kPointSrc = false>
-__global__ void __launch_bounds__(kBlock, kWaves) k_chain(ChainArgs a) {
+// The two walks of the chain kernels over the rays of a launch (or of a batched system), a: its
+// arguments, fg: its maps (a mode with figure terms) or nullptr. Macros for the same reason as
+// AKB_MIRROR_BY_KIND: with a walk in a function of its own, optimised before the kernel sees it, the
+// kernels around it compiled to other code (k_chain_batch with 7 more VGPRs and spilled SGPRs).
+// Grid-stride over workgroup-sized segments, every requested row written per ray:
+#define AKB_WALK_ROWS(M, a, fg)                                                                       \
+    do {                                                                                             \
+        int fl = 0;                                                                                  \
+        double qv[5];                                                                                \
+        const int t = threadIdx.x;                                                                   \
+        for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock) \
+            if (i0 + t < a.n) chain_ray<M>(a, i0, t, fl, qv, fg);                                    \
+        if (fl) atomicOr(a.flags, fl);                                                               \
+    } while (0)
+// 256-ray segments, feeding the fused np.nanmean(arctan) / np.mean(det) leaf sums (the tilt means,
+// ref :3583-3591) instead of writing those five rows to HBM:
+#define AKB_WALK_SINK(M, a, fg)                                                  \
+    do {                                                                        \
+        __shared__ LeafLds<5> L;                                                \
+        int fl = 0;                                                             \
+        const int t = threadIdx.x;                                              \
+        const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;                   \
+        for (int64_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {          \
+            const bool valid = seg * kLeafSeg + t < a.n;                        \
+            double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                           \
+            if (valid) chain_ray<M>(a, seg * kLeafSeg, t, fl, qv, fg);          \
+            leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);         \
+        }                                                                       \
+        if (fl) atomicOr(a.flags, fl);                                          \
+    } while (0)
+
+// the chain kernels at 4 waves per SIMD (the register allocator's floor; pass 2's fixed-output
+// sink: 89 VGPRs and no scratch; 6 waves spilled 8 VGPRs and was no faster, 8 spilled 160 B and
+// was slower)
+constexpr int kChainWaves = 4;
+
+// per-ray rows. kPointSrc: grid rays from the point source (no origin loads)
+template <bool kGrid, bool kOPL, bool kHits = false, bool kPointSrc = false>
+__global__ void __launch_bounds__(kBlock, kChainWaves) k_chain(ChainArgs a) {
     stage_copy(a);
-    int fl = 0;
-    double qv[5];
-    const int t = threadIdx.x;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
-        if (i0 + t < a.n) chain_ray<kGrid, kOPL, false, kHits, false, kPointSrc>(a, i0, t, fl, qv);
-    if (fl) atomicOr(a.flags, fl);
+    using M = RowsMode<kGrid, kOPL, kHits, kPointSrc>;
+    AKB_WALK_ROWS(M, a, nullptr);
 }
 
 // k_chain with the mirrors' figure terms (always with the OPL row); kSlope: the mapped mirrors
@@ -963,12 +1016,8 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain(ChainArgs a) {
 template <bool kGrid, bool kHits, bool kSlope = false, bool kOPL = true>
 __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_fig(ChainArgsFig a) {
     stage_copy(a);
-    int fl = 0;
-    double qv[5];
-    const int t = threadIdx.x;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
-        if (i0 + t < a.n) chain_ray<kGrid, kOPL, false, kHits, false, false, false, true, kSlope>(a, i0, t, fl, qv, &a.fig);
-    if (fl) atomicOr(a.flags, fl);
+    using M = RowsMode<kGrid, kOPL, kHits, false, kSlope ? kMapsDeflect : kMapsPath>;
+    AKB_WALK_ROWS(M, a, &a.fig);
 }
 
 // The chain as the reference runs it with option_mpmath set: only mirr_ray_intersection and
@@ -1067,42 +1116,26 @@ __global__ void __launch_bounds__(kBlock) k_chain_dd(ChainArgs a) {
     if (fl) atomicOr(a.flags, fl);
 }
 
-// the same, walking 256-ray segments and feeding the fused np.nanmean(arctan) / np.mean(det)
-// leaf sums (the tilt means, ref :3583-3591) instead of writing those five rows to HBM
+// the leaf sums (AKB_WALK_SINK) where k_chain would write the detector and arctan rows
 // kPointSrc: grid rays from the point source (no origin loads)
-// kFixed: pass 2 of RayWave (chain_ray_tab's fixed output set)
-template <bool kGrid, bool kOPL, int kWaves, bool kPointSrc = false, bool kFixed = false>
-__global__ void __launch_bounds__(kBlock, kWaves) k_chain_sink(ChainArgs a) {
+// kFixed: pass 2 of RayWave (chain_ray_tab's fixed output set; grid rays from the point source with OPL)
+template <bool kGrid, bool kOPL, bool kPointSrc = false, bool kFixed = false>
+__global__ void __launch_bounds__(kBlock, kChainWaves) k_chain_sink(ChainArgs a) {
+    static_assert(!kFixed || (kGrid && kOPL && kPointSrc), "the fixed output set is pass 2's");
     stage_copy(a);
-    __shared__ LeafLds<5> L;
-    int fl = 0;
-    const int t = threadIdx.x;
-    const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;
-    for (int64_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const bool valid = seg * kLeafSeg + t < a.n;
-        double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (valid) chain_ray<kGrid, kOPL, true, false, false, kPointSrc, kFixed>(a, seg * kLeafSeg, t, fl, qv);
-        leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);
-    }
-    if (fl) atomicOr(a.flags, fl);
+    using M = std::conditional_t<kFixed, FixedPass2<>, SinkMode<kGrid, kOPL, kPointSrc>>;
+    AKB_WALK_SINK(M, a, nullptr);
 }
 
-// k_chain_sink with the mirrors' figure terms; kFixed (grid rays from the point source, RayWave's
-// pass-2 output set) as there
+// k_chain_sink with the mirrors' figure terms (always with the OPL row); kFixed (grid rays from the
+// point source, RayWave's pass-2 output set) as there, every other launch with per-ray origins
 template <bool kGrid, bool kFixed, bool kSlope = false>
 __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_sink_fig(ChainArgsFig a) {
+    static_assert(!kFixed || kGrid, "the fixed output set is pass 2's");
+    constexpr FigMaps kMaps = kSlope ? kMapsDeflect : kMapsPath;
     stage_copy(a);
-    __shared__ LeafLds<5> L;
-    int fl = 0;
-    const int t = threadIdx.x;
-    const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;
-    for (int64_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const bool valid = seg * kLeafSeg + t < a.n;
-        double qv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (valid) chain_ray<kGrid, true, true, false, false, kFixed, kFixed, true, kSlope>(a, seg * kLeafSeg, t, fl, qv, &a.fig);
-        leaf_sink_segment<5>(a.sink, L, seg * kLeafSeg, qv, valid);
-    }
-    if (fl) atomicOr(a.flags, fl);
+    using M = std::conditional_t<kFixed, FixedPass2<kMaps>, SinkMode<kGrid, true, false, kMaps>>;
+    AKB_WALK_SINK(M, a, &a.fig);
 }
 
 // S independent grid systems in one launch: auto_focus_NA and calc_FoC trace many small systems
@@ -1112,12 +1145,8 @@ __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_sink_fig(ChainArgsF
 template <bool kOPL, bool kHits>
 __global__ void __launch_bounds__(kBlock) k_chain_batch(const ChainArgs* __restrict__ A) {
     const ChainArgs& a = A[blockIdx.y];
-    int fl = 0;
-    double qv[5];
-    const int t = threadIdx.x;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
-        if (i0 + t < a.n) chain_ray<true, kOPL, false, kHits, false, false>(a, i0, t, fl, qv);
-    if (fl) atomicOr(a.flags, fl);
+    using M = RowsMode<true, kOPL, kHits, false>;
+    AKB_WALK_ROWS(M, a, nullptr);
 }
 
 // k_chain_batch for systems whose mapped mirrors deflect (fig_slope): the per-system arguments, maps
@@ -1125,13 +1154,11 @@ __global__ void __launch_bounds__(kBlock) k_chain_batch(const ChainArgs* __restr
 template <bool kOPL, bool kHits>
 __global__ void __launch_bounds__(kBlock, kFigWaves) k_chain_batch_fig(const ChainArgsFig* __restrict__ A) {
     const ChainArgsFig& a = A[blockIdx.y];
-    int fl = 0;
-    double qv[5];
-    const int t = threadIdx.x;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock; i0 < a.n; i0 += (int64_t)gridDim.x * kBlock)
-        if (i0 + t < a.n) chain_ray<true, kOPL, false, kHits, false, false, false, true, true>(a, i0, t, fl, qv, &a.fig);
-    if (fl) atomicOr(a.flags, fl);
+    using M = RowsMode<true, kOPL, kHits, false, kMapsDeflect>;
+    AKB_WALK_ROWS(M, a, &a.fig);
 }
+#undef AKB_WALK_ROWS
+#undef AKB_WALK_SINK
 
 // ----------------------------------------------------------------------------------------------
 // tilt correction + detectors + OPL (ref AKB_raytrace_20250312.py:3583-3601, :3611-3633)
@@ -1580,7 +1607,7 @@ __global__ void __launch_bounds__(kBlock, kWaves) k_chain_tilt(ChainArgs a, Tilt
         double d2[3], tq[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
         OpdIn oin;
         if (valid)
-            chain_ray_tab<true, false, false, false, true, true>(a, i0, t, iv, ih, th, tv, fl, qv, [&] {
+            chain_ray_tab<LeanPass1>(a, i0, t, iv, ih, th, tv, fl, qv, [&] {
                 if constexpr (kOPD) opd_load(o, b.ld, i0, off, oin);
                 tilt_compute(b, in, d2, tq);
                 // every value that reads this segment's `in` is formed above this line, so the
@@ -1694,39 +1721,25 @@ using namespace akb;
 
 static inline V3In v3in(const double* p, int64_t ld, int64_t inc) { return V3In{p, ld, inc}; }
 
-// the chain kernels at 4 waves per SIMD (the register allocator's floor; pass 2's fixed-output
-// sink: 89 VGPRs and no scratch; 6 waves spilled 8 VGPRs and was no faster, 8 spilled 160 B and
-// was slower), workgroups capped at 8192 (each walks 256-ray segments grid-stride; measured best
-// for the unfused passes; the fused pass 1 takes kPass1Rounds rounds of resident workgroups,
+// the chain kernels' workgroups capped at 8192 (each walks 256-ray segments grid-stride; measured
+// best for the unfused passes; the fused pass 1 takes kPass1Rounds rounds of resident workgroups,
 // chain_tilt below); the OPD kernel at 2048 (its extent atomics grow with the grid)
-constexpr int kChainWaves = 4;
 constexpr int64_t kChainGridCap = 256 * 32;
 constexpr int64_t kOpdGridCap = 2048;
 
-template <bool kGrid, bool kOPL, bool kSink>
-static void launch_chain(int w, unsigned g, hipStream_t s, const ChainArgs& a) {
-    if (!kSink && a.hits) {  // per-mirror hit rows (the stage-equivalent outputs): one variant
-        k_chain<kGrid, kOPL, 4, true><<<g, kBlock, 0, s>>>(a);
-        return;
-    }
-    // rays from the point source: the variant without origin loads (grid rays only)
-    const bool point = kGrid && a.org == nullptr;
-    // RayWave's pass 2: exactly the last hit, exit direction and OPL rows
-    const bool fixed = kGrid && kOPL && point && a.last_hit && a.dir_out && a.opl && !a.det_out && !a.atan_h &&
-                       !a.atan_v && !a.samp_h && !a.samp_v && !a.hits;
-    if (kSink && fixed) {
-        k_chain_sink<kGrid, kOPL, kChainWaves, kGrid, kGrid && kOPL><<<g, kBlock, 0, s>>>(a);
-        return;
-    }
-    (void)w;
-    if (kSink && point)
-        k_chain_sink<kGrid, kOPL, kChainWaves, kGrid><<<g, kBlock, 0, s>>>(a);
-    else if (kSink)
-        k_chain_sink<kGrid, kOPL, kChainWaves, false><<<g, kBlock, 0, s>>>(a);
-    else if (point)
-        k_chain<kGrid, kOPL, kChainWaves, false, kGrid><<<g, kBlock, 0, s>>>(a);
+// f(c...) with each runtime bool as a std::true_type / std::false_type c: the kernels' compile-time
+// switches chosen at run time. A launch under `if constexpr` on the c's instantiates no kernel for
+// the combinations that no descriptor reaches.
+template <class F>
+static void with_bools(F&& f) {
+    f();
+}
+template <class F, class... Bs>
+static void with_bools(F&& f, bool b, Bs... rest) {
+    if (b)
+        with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
     else
-        k_chain<kGrid, kOPL, kChainWaves, false, false><<<g, kBlock, 0, s>>>(a);
+        with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 extern "C" {
@@ -1988,6 +2001,12 @@ static int chain_args_from(const akb_chain_desc* d, ChainArgs& a, bool& empty) {
         empty = true;
         return AKB_OK;
     }
+    // a row shorter than the launch would be written past its end
+    if (d->hits) AKB_REQUIRE(d->hits_ld >= d->n_rays, "hits_ld < n_rays");
+    if (d->last_hit) AKB_REQUIRE(d->last_hit_ld >= d->n_rays, "last_hit_ld < n_rays");
+    if (d->dir_out) AKB_REQUIRE(d->dir_out_ld >= d->n_rays, "dir_out_ld < n_rays");
+    if (d->det_out) AKB_REQUIRE(d->det_out_ld >= d->n_rays, "det_out_ld < n_rays");
+    if (grid) AKB_REQUIRE(d->samp_h == nullptr || d->samp_h_end >= d->samp_h_begin, "bad samp_h range");
     a.K = d->n_mirrors;
     for (int k = 0; k < d->n_mirrors; ++k) {
         const double* c = d->coeffs[k];
@@ -2151,61 +2170,52 @@ static int fig_args_from(const akb_chain_desc* d, const ChainArgs& a, ChainArgsF
 
 }  // extern "C" (templates have C++ linkage)
 
-// k_chain_fig with or without the OPL row; without kSlope the row is always there (both branches name
-// the same instantiation)
-template <bool kGrid, bool kHits, bool kSlope>
-static void launch_k_chain_fig(bool opl, unsigned g, hipStream_t s, const ChainArgsFig& f) {
-    if (opl)
-        k_chain_fig<kGrid, kHits, kSlope, true><<<g, kBlock, 0, s>>>(f);
-    else
-        k_chain_fig<kGrid, kHits, kSlope, !kSlope><<<g, kBlock, 0, s>>>(f);
-}
-
-// the dispatch over the figure kernels' instantiations, the plain chain's grids
-template <bool kSlope>
-static int launch_fig_kernels(const akb_chain_desc* d, const ChainArgs& a, const ChainArgsFig& f, hipStream_t s) {
-    const bool grid = d->dir == nullptr;
-    if (d->sink.nq > 0) {
-        const int64_t nseg = (d->n_rays + kLeafSeg - 1) / kLeafSeg;
-        const unsigned gs = (unsigned)(nseg < kChainGridCap ? nseg : kChainGridCap);
-        // RayWave's pass 2, as launch_chain picks it
-        const bool fixed = grid && a.org == nullptr && a.last_hit && a.dir_out && !a.det_out && !a.atan_h &&
-                           !a.atan_v && !a.samp_h && !a.samp_v && !a.hits;
-        if (fixed)
-            k_chain_sink_fig<true, true, kSlope><<<gs, kBlock, 0, s>>>(f);
-        else if (grid)
-            k_chain_sink_fig<true, false, kSlope><<<gs, kBlock, 0, s>>>(f);
-        else
-            k_chain_sink_fig<false, false, kSlope><<<gs, kBlock, 0, s>>>(f);
+// The one dispatch of a single launch: the kernel for what the arguments ask for. The instantiations
+// it names are the whole set; the kernels' grids are the plain chain's. In the lambdas
+// G: grid rays, O: the OPL row, H: the hit rows, P: from the point source, X: the fixed output set,
+// S: the maps deflect - the kernels' template parameters, in each kernel's order.
+static int launch_chain(const ChainArgsFig& f, FigMaps maps, hipStream_t s) {
+    const ChainArgs& a = f;
+    const bool grid = a.dir == nullptr;              // rays from the angle tables, or explicit directions
+    const bool point = grid && a.org == nullptr;     // from the point source: no origin loads (grid rays only)
+    const bool opl = a.opl != nullptr, hits = a.hits != nullptr;
+    const bool slope = maps == kMapsDeflect;
+    if (a.sink.nq > 0) {
+        const int64_t nseg = (a.n + kLeafSeg - 1) / kLeafSeg;
+        const unsigned g = (unsigned)(nseg < kChainGridCap ? nseg : kChainGridCap);
+        // RayWave's pass 2: exactly the last hit, exit direction and OPL rows
+        const bool fixed = point && opl && a.last_hit && a.dir_out && !a.det_out && !a.atan_h && !a.atan_v &&
+                           !a.samp_h && !a.samp_v && !hits;
+        if (maps == kNoMaps) {
+            with_bools([&](auto G, auto O, auto P, auto X) {
+                // the fixed set is one kernel; explicit rays have no point-source variant
+                if constexpr (X ? G && O && P : G || !P) k_chain_sink<G, O, P, X><<<g, kBlock, 0, s>>>(a);
+            }, grid, opl, point, fixed);
+            return launch_status("k_chain_sink");
+        }
+        // with maps the OPL row is always there (launch_chain's caller checks), and only pass 2 skips
+        // the origin test
+        with_bools([&](auto G, auto X, auto S) {
+            if constexpr (G || !X) k_chain_sink_fig<G, X, S><<<g, kBlock, 0, s>>>(f);
+        }, grid, fixed, slope);
         return launch_status("k_chain_sink_fig");
     }
-    const unsigned g = grid_for(d->n_rays, 1, kChainGridCap);
-    const bool opl = d->opl != nullptr;
-    if (grid && a.hits)
-        launch_k_chain_fig<true, true, kSlope>(opl, g, s, f);
-    else if (grid)
-        launch_k_chain_fig<true, false, kSlope>(opl, g, s, f);
-    else if (a.hits)
-        launch_k_chain_fig<false, true, kSlope>(opl, g, s, f);
-    else
-        launch_k_chain_fig<false, false, kSlope>(opl, g, s, f);
+    const unsigned g = grid_for(a.n, 1, kChainGridCap);
+    if (maps == kNoMaps) {
+        // per-mirror hit rows (the stage-equivalent outputs): one variant, with the origin test
+        with_bools([&](auto G, auto O, auto H, auto P) {
+            if constexpr ((G || !P) && !(H && P)) k_chain<G, O, H, P><<<g, kBlock, 0, s>>>(a);
+        }, grid, opl, hits, point && !hits);
+        return launch_status("k_chain");
+    }
+    // maps that only add their path term always come with the OPL row
+    with_bools([&](auto G, auto H, auto S, auto O) {
+        if constexpr (S || O) k_chain_fig<G, H, S, O><<<g, kBlock, 0, s>>>(f);
+    }, grid, hits, slope, opl || !slope);
     return launch_status("k_chain_fig");
 }
 
 extern "C" {
-
-// the chain with figure maps: its own kernels (k_chain_fig / k_chain_sink_fig), the plain chain's grids
-static int launch_chain_fig(const akb_chain_desc* d, const ChainArgs& a, hipStream_t s) {
-    const bool slope = d->fig_slope != 0;
-    // the path term needs the OPL row; maps that only deflect (fig_slope) do without it
-    AKB_REQUIRE(d->opl != nullptr || (slope && d->fig_out == nullptr),
-                "figure maps add to the optical path: the descriptor needs opl (or fig_slope and no fig_out)");
-    AKB_REQUIRE(d->opl != nullptr || d->sink.nq == 0, "the chain sink with figure maps needs opl");
-    ChainArgsFig f;
-    const int fst = fig_args_from(d, a, f);
-    if (fst != AKB_OK) return fst;
-    return slope ? launch_fig_kernels<true>(d, a, f, s) : launch_fig_kernels<false>(d, a, f, s);
-}
 
 int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
     clear_error();
@@ -2213,38 +2223,18 @@ int akb_trace_chain_f64(const akb_chain_desc* d, void* stream) {
     bool empty;
     const int st = chain_args_from(d, a, empty);
     if (st != AKB_OK || empty) return st;
-    const bool grid = d->dir == nullptr;
-    const bool sink = d->sink.nq > 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (desc_has_fig(d)) return launch_chain_fig(d, a, s);
-    const int64_t gcap = kChainGridCap;
-    const unsigned gsz = grid_for(d->n_rays, 1, gcap);
-    const int w = kChainWaves;
-    if (sink) {
-        const int64_t nseg = (d->n_rays + kLeafSeg - 1) / kLeafSeg;
-        const unsigned gs = (unsigned)(nseg < gcap ? nseg : gcap);
-        if (grid && d->opl)
-            launch_chain<true, true, true>(w, gs, s, a);
-        else if (grid)
-            launch_chain<true, false, true>(w, gs, s, a);
-        else if (d->opl)
-            launch_chain<false, true, true>(w, gs, s, a);
-        else
-            launch_chain<false, false, true>(w, gs, s, a);
-        return launch_status("k_chain_sink");
+    FigMaps maps = kNoMaps;
+    if (desc_has_fig(d)) {
+        maps = d->fig_slope != 0 ? kMapsDeflect : kMapsPath;
+        // the path term needs the OPL row; maps that only deflect (fig_slope) do without it
+        AKB_REQUIRE(d->opl != nullptr || (maps == kMapsDeflect && d->fig_out == nullptr),
+                    "figure maps add to the optical path: the descriptor needs opl (or fig_slope and no fig_out)");
+        AKB_REQUIRE(d->opl != nullptr || d->sink.nq == 0, "the chain sink with figure maps needs opl");
     }
-    if (grid) {
-        if (d->opl)
-            launch_chain<true, true, false>(w, gsz, s, a);
-        else
-            launch_chain<true, false, false>(w, gsz, s, a);
-    } else {
-        if (d->opl)
-            launch_chain<false, true, false>(w, gsz, s, a);
-        else
-            launch_chain<false, false, false>(w, gsz, s, a);
-    }
-    return launch_status("k_chain");
+    ChainArgsFig f;  // without maps: the plain arguments and no table
+    const int fst = fig_args_from(d, a, f);
+    if (fst != AKB_OK) return fst;
+    return launch_chain(f, maps, (hipStream_t)stream);
 }
 
 int akb_trace_chain_dd_f64(const akb_chain_desc* d, void* stream) {
@@ -2268,11 +2258,6 @@ int akb_trace_chain_dd_f64(const akb_chain_desc* d, void* stream) {
         return AKB_E_ARG;
     }
     if (empty) return AKB_OK;
-    if (d->hits) AKB_REQUIRE(d->hits_ld >= d->n_rays, "hits_ld < n_rays");
-    if (d->last_hit) AKB_REQUIRE(d->last_hit_ld >= d->n_rays, "last_hit_ld < n_rays");
-    if (d->dir_out) AKB_REQUIRE(d->dir_out_ld >= d->n_rays, "dir_out_ld < n_rays");
-    if (d->det_out) AKB_REQUIRE(d->det_out_ld >= d->n_rays, "det_out_ld < n_rays");
-    if (d->dir == nullptr) AKB_REQUIRE(d->samp_h == nullptr || d->samp_h_end >= d->samp_h_begin, "bad samp_h range");
     k_chain_dd<<<grid_for(d->n_rays, 1, kDDGridCap), kBlock, 0, (hipStream_t)stream>>>(a);
     return launch_status("k_chain_dd");
 }
@@ -2549,14 +2534,7 @@ int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stre
         int st = stage_args(fargs.data(), sizeof(ChainArgsFig) * fargs.size(), s, &d_args);
         if (st != AKB_OK) return st;
         const ChainArgsFig* A = (const ChainArgsFig*)d_args;
-        if (opl && hits)
-            k_chain_batch_fig<true, true><<<grid, kBlock, 0, s>>>(A);
-        else if (opl)
-            k_chain_batch_fig<true, false><<<grid, kBlock, 0, s>>>(A);
-        else if (hits)
-            k_chain_batch_fig<false, true><<<grid, kBlock, 0, s>>>(A);
-        else
-            k_chain_batch_fig<false, false><<<grid, kBlock, 0, s>>>(A);
+        with_bools([&](auto O, auto H) { k_chain_batch_fig<O, H><<<grid, kBlock, 0, s>>>(A); }, opl, hits);
         st = launch_status("k_chain_batch_fig");
         AKB_HIP_CHECK(hipFreeAsync(d_args, s));
         return st;
@@ -2564,14 +2542,7 @@ int akb_trace_chain_batch_f64(const akb_chain_desc* descs, int n_sys, void* stre
     int st = stage_args(args.data(), sizeof(ChainArgs) * args.size(), s, &d_args);
     if (st != AKB_OK) return st;
     const ChainArgs* A = (const ChainArgs*)d_args;
-    if (opl && hits)
-        k_chain_batch<true, true><<<grid, kBlock, 0, s>>>(A);
-    else if (opl)
-        k_chain_batch<true, false><<<grid, kBlock, 0, s>>>(A);
-    else if (hits)
-        k_chain_batch<false, true><<<grid, kBlock, 0, s>>>(A);
-    else
-        k_chain_batch<false, false><<<grid, kBlock, 0, s>>>(A);
+    with_bools([&](auto O, auto H) { k_chain_batch<O, H><<<grid, kBlock, 0, s>>>(A); }, opl, hits);
     st = launch_status("k_chain_batch");
     AKB_HIP_CHECK(hipFreeAsync(d_args, s));
     return st;
@@ -2595,13 +2566,15 @@ int akb_trace_chain_samples_f64(const akb_chain_desc* d, void* stream) {
     a.cp_n = 0;
     a.pert_h = a.pert_v = nullptr;
     hipStream_t s = (hipStream_t)stream;
+    // grid rays, no OPL, no hit rows, with the origin test (launch_chain's kernel for such a launch)
+    const auto k_picks = k_chain<true, false, false, false>;
     if (has_h) {  // the middle-row range: contiguous flat indices
         ChainArgs r = a;
         r.samp_v = nullptr;
         r.g0 = d->samp_h_begin;
         r.g_stride = 1;
         r.n = d->samp_h_end - d->samp_h_begin;
-        k_chain<true, false, 4><<<grid_for(r.n), kBlock, 0, s>>>(r);
+        k_picks<<<grid_for(r.n), kBlock, 0, s>>>(r);
         const int e = launch_status("k_chain (picks, row)");
         if (e != AKB_OK) return e;
     }
@@ -2611,7 +2584,7 @@ int akb_trace_chain_samples_f64(const akb_chain_desc* d, void* stream) {
         c.g0 = d->samp_v_col;
         c.g_stride = d->n_h;
         c.n = d->n_v;
-        k_chain<true, false, 4><<<grid_for(c.n), kBlock, 0, s>>>(c);
+        k_picks<<<grid_for(c.n), kBlock, 0, s>>>(c);
         return launch_status("k_chain (picks, column)");
     }
     return AKB_OK;
@@ -2672,13 +2645,10 @@ static int chain_tilt(const akb_chain_desc* d, const double* d_params, const dou
     // would allow four) leave every SIMD a wave of 128 VGPRs and 38 KB of LDS, where the faithful
     // chain's 256-thread workgroups run beside the pass instead of waiting for it to drain a CU
     constexpr size_t kPass1LdsPad = 22528;
-#define AKB_CT(W)                                                  \
-    if (o)                                                         \
-        k_chain_tilt<W, true><<<gs, kBlock, kPass1LdsPad, s>>>(a, b, *o);     \
-    else                                                           \
-        k_chain_tilt<W, false><<<gs, kBlock, kPass1LdsPad, s>>>(a, b, no);
-    AKB_CT(kChainWaves)
-#undef AKB_CT
+    if (o)
+        k_chain_tilt<kChainWaves, true><<<gs, kBlock, kPass1LdsPad, s>>>(a, b, *o);
+    else
+        k_chain_tilt<kChainWaves, false><<<gs, kBlock, kPass1LdsPad, s>>>(a, b, no);
     return launch_status("k_chain_tilt");
 }
 

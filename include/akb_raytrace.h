@@ -237,7 +237,9 @@ typedef struct akb_chain_desc {
     int64_t n_rays;                          /* rays in this launch */
     const double* org; int64_t org_ld; int64_t org_inc; /* NULL => constant source src[] */
     double src[3];
-    /* outputs (any may be NULL) */
+    /* outputs (any may be NULL). A row that is asked for has a leading dimension of at least n_rays:
+     * every entry point that takes a descriptor (the fp64, double-double and batch chains, the picks,
+     * the fused pass 1) refuses a shorter one before it launches anything, AKB_E_ARG. */
     double* hits; int64_t hits_ld;           /* K blocks of (3, hits_ld): mirror hit points */
     double* last_hit; int64_t last_hit_ld;   /* (3, ld) point on the last mirror */
     double* dir_out; int64_t dir_out_ld;     /* (3, ld) direction after the last mirror */
