@@ -36,6 +36,7 @@ EXPORTS = [
     "akb_isect_f64", "akb_normal_f64", "akb_reflect_f64", "akb_normalize_f64", "akb_plane_isect_f64",
     "akb_seglen_f64", "akb_rotate_f64", "akb_fill_nan_f64",
     "akb_isect_dd_f64", "akb_reflect_dd_f64", "akb_trace_chain_dd_f64", "akb_figure_opl_f64", "akb_figure_normal_f64",
+    "akb_figure_displace_f64",
     "akb_trace_chain_f64", "akb_chain_desc_size", "akb_tilt_opd_f64", "akb_tilt_params_f64",
     "akb_tilt_opd_dev_f64", "akb_chain_tilt_f64", "akb_chain_tilt_opd_f64", "akb_trace_chain_samples_f64", "akb_opd_f64", "akb_resample_f64", "akb_plane_sweep_rows_f64",
     "akb_plane_sweep_sink_f64",
@@ -129,6 +130,8 @@ def _declare(L):
         "akb_figure_opl_f64": ([ctypes.POINTER(FigureMapDesc), c_vp] + v3 + v3 + [c_i64, c_vp, c_int, c_vp, c_vp], c_int),
         "akb_figure_normal_f64": ([ctypes.POINTER(FigureMapDesc), c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
                                    c_vp], c_int),
+        "akb_figure_displace_f64": ([ctypes.POINTER(FigureMapDesc), c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
+                                     c_vp, c_vp], c_int),
         "akb_normalize_f64": (v3 + [c_i64, c_vp, c_i64, c_vp, c_vp], c_int),
         "akb_plane_isect_f64": ([c_vp] + v3 + v3 + [c_i64, c_vp, c_i64, c_vp], c_int),
         "akb_seglen_f64": (v3 + v3 + [c_i64, c_vp, c_vp], c_int),

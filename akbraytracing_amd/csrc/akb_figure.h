@@ -43,6 +43,19 @@
 //     e_u, e_w are the frame's, and across a footprint the quadric's normal turns by milliradians.
 //   N' replaces N in the reflection only (reflect_ray's order, A = (l nx + m ny) + n nz, all three
 //     components whatever the mirror's kind); the path term keeps the quadric's own N.
+//
+// Displaced points (the wave chain): the Huygens sum samples each mirror at the traced hit
+// points, so a map moves every sample along the surface normal by its height there - no wavelength
+// enters, and no load beyond locate()'s sixteen.
+//   dn = (l nx + m ny) + n nz (dot_dn) with N the quadric's unit normal at the hit and d = (l, m, n) the
+//     incoming direction; only the sign of dn is read, so d need not be unit
+//   sigma = (dn > 0) ? -1 : 1 (deflect's rule: sigma N points towards the incoming beam)
+//   h = combine() of the sixteen samples, as in eval
+//   s = sigma * h
+//   x' = x + s * nx, y' = y + s * ny, z' = z + s * nz
+//   a hit outside the map returns (x, y, z) themselves (a select, not P + 0 N) and reports it; a NaN
+//     hit gives NaN and no report
+// Positive h is a bump towards the incoming beam, as above.
 #pragma once
 
 #include <math.h>
@@ -161,6 +174,18 @@ AKB_FIG_FN void deflect(double& nx, double& ny, double& nz, double dn, const Map
     nz = outside ? nz : z / s;
 }
 
+// the displaced point P' = P + (sigma h) N in place of the hit (x, y, z); (nx, ny, nz) the unit normal,
+// dn = d . N
+AKB_FIG_FN void displace(double& x, double& y, double& z, double nx, double ny, double nz, double dn, double h,
+                         bool outside) {
+    const double sigma = dn > 0.0 ? -1.0 : 1.0;
+    const double s = sigma * h;
+    const double px = x + s * nx, py = y + s * ny, pz = z + s * nz;
+    x = outside ? x : px;
+    y = outside ? y : py;
+    z = outside ? z : pz;
+}
+
 // the path term from the height and d . n
 AKB_FIG_FN double path_term(double h, double dn) { return (-2.0 * h) * fabs(dn); }
 
@@ -195,6 +220,20 @@ AKB_FIG_FN bool eval_normal(const Map& M, double x, double y, double z, double l
     for (int k = 0; k < 16; ++k) v[k] = M.h[off[k]];
     gradient(v, tu, tw, M, o, hu, hw);
     deflect(nx, ny, nz, dot_dn(l, m, n, nx, ny, nz), M, hu, hw, o);
+    return o;
+}
+
+// the displaced point for one hit with the unit normal (nx, ny, nz) and the incoming direction
+// (l, m, n): P' in place, the interpolated height in h (+0 outside); returns true for a hit outside
+// the map (P untouched)
+AKB_FIG_FN bool eval_displace(const Map& M, double& x, double& y, double& z, double l, double m, double n, double nx,
+                              double ny, double nz, double& h) {
+    int32_t off[16];
+    double tu, tw, v[16];
+    const bool o = locate(M, x, y, z, off, tu, tw);
+    for (int k = 0; k < 16; ++k) v[k] = M.h[off[k]];
+    h = combine(v, tu, tw, o);
+    displace(x, y, z, nx, ny, nz, dot_dn(l, m, n, nx, ny, nz), h, o);
     return o;
 }
 

@@ -180,7 +180,31 @@ __global__ void __launch_bounds__(kBlock) k_figure_normal(akb_fig::Map M, Quadri
     if (fl) atomicOr(flags, fl);
 }
 
-__global__ void __launch_bounds__(kBlock) k_plane(double g, double h, double ii, double j, V3In dir,
+// one mirror's displaced sample points from materialised hits and incoming directions (akb_figure.h's
+// displace): the hit moved along k_normal's unit normal by the map's height, turned towards the
+// incoming beam; the hit itself outside the map or where the normal has zero norm. The same gathers
+// as k_figure_opl.
+__global__ void __launch_bounds__(kBlock) k_figure_displace(akb_fig::Map M, Quadric Q, V3In hit, V3In dir, int64_t n,
+                                                            V3Out out, double* h_out, int32_t* flags) {
+    int fl = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double x = hit.x(i), y = hit.y(i), z = hit.z(i);
+        double nx, ny, nz;
+        quadric_grad(Q, x, y, z, nx, ny, nz);
+        const double s = norm3(nx, ny, nz);
+        const bool zero = s == 0.0;
+        if (zero) fl |= AKB_FLAG_ZERO_NORMAL;
+        double px = x, py = y, pz = z, h;
+        if (akb_fig::eval_displace(M, px, py, pz, dir.x(i), dir.y(i), dir.z(i), nx / s, ny / s, nz / s, h))
+            fl |= AKB_FLAG_FIG_OUTSIDE;
+        out.store(i, zero ? x : px, zero ? y : py, zero ? z : pz);
+        if (h_out) h_out[i] = h;
+    }
+    if (fl) atomicOr(flags, fl);
+}
+
+__global__ void __launch_bounds__(kBlock) k_plane(double g,double h, double ii, double j, V3In dir,
                                                   V3In org, int64_t n, V3Out out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -2152,6 +2176,30 @@ int akb_figure_normal_f64(const akb_figure_map* map, const double coeffs[10], co
     k_figure_normal<<<grid_for(n, 1, kStreamGridCap), kBlock, 0, (hipStream_t)stream>>>(
         M, quadric_from(coeffs), v3in(hit, hit_ld, 1), v3in(dir, dir_ld, 1), n, V3Out{normal_out, normal_ld}, flags);
     return launch_status("k_figure_normal");
+}
+
+// whether two (3, ld) blocks of n columns share an address
+static bool rows_overlap(const double* a, int64_t a_ld, const double* b, int64_t b_ld, int64_t n) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = (uintptr_t)(a + 2 * a_ld + n);
+    const uintptr_t b0 = (uintptr_t)b, b1 = (uintptr_t)(b + 2 * b_ld + n);
+    return a0 < b1 && b0 < a1;
+}
+
+int akb_figure_displace_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                            const double* dir, int64_t dir_ld, int64_t n, double* out, int64_t out_ld, double* h_out,
+                            int32_t* flags, void* stream) {
+    clear_error();
+    AKB_REQUIRE(map && coeffs && hit && dir && out && flags, "null pointer");
+    AKB_REQUIRE(n >= 0 && hit_ld >= n && dir_ld >= n && out_ld >= n, "bad sizes");
+    akb_fig::Map M;
+    const int st = fig_map_from(map, M);
+    if (st != AKB_OK) return st;
+    if (n == 0) return AKB_OK;
+    AKB_REQUIRE(!rows_overlap(out, out_ld, hit, hit_ld, n) && !rows_overlap(out, out_ld, dir, dir_ld, n),
+                "out overlaps hit or dir");
+    k_figure_displace<<<grid_for(n, 1, kStreamGridCap), kBlock, 0, (hipStream_t)stream>>>(
+        M, quadric_from(coeffs), v3in(hit, hit_ld, 1), v3in(dir, dir_ld, 1), n, V3Out{out, out_ld}, h_out, flags);
+    return launch_status("k_figure_displace");
 }
 
 // the kernel arguments with the descriptor's maps

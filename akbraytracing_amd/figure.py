@@ -21,6 +21,11 @@ The ray-spot modes (the batched 'test' trace, auto_focus_NA, calc_FoC; trace_cha
 also let the map deflect the ray: the reflection takes N' = (N - sigma g) / ||N - sigma g|| with
 g = dh/du e_u + dh/dw e_w the map's gradient and sigma N the normal turned towards the incoming beam
 (DESIGN 7.5). stage_normals is that trace stage by stage. The wavefront modes keep the thin screen.
+
+The wave chain (wavedata.saveWaveData / plot_result_wave / kb_wave with figure=, then run_wave_chain)
+samples each mirror at the traced hit points, so there the map moves every sample along the normal:
+P' = P + sigma h N (displace, displace_hits; akb_figure_displace_f64). sampling compares a
+grid's sample spacing with the map's pitch.
 """
 import numpy as np
 
@@ -251,6 +256,68 @@ def figure_normal(fm, coeffs, hit, ray):
     _lib.check(_lib.lib().akb_figure_normal_f64(fm.desc(hit.device), D.host_f64(coeffs), D.ptr(hit), n, D.ptr(ray), n, n,
                                                 D.ptr(out), n, D.ptr(fl), D.stream_handle()))
     return out, int(fl.item())
+
+
+def displace(fm, coeffs, hit, dirs, want_height=False):
+    """One mirror's displaced sample points (akb_figure_displace_f64) from hits and incoming directions
+    (only the sign of d . N is read: they need not be unit), (3, n) device tensors: P' = P + sigma h N,
+    P itself outside the map. Returns ((3, n) points, the kernel's flag word[, the heights (n)])."""
+    import torch
+
+    from . import device as D
+    n = hit.shape[1]
+    hit, dirs = hit.contiguous(), dirs.contiguous()
+    out = torch.empty((3, n), dtype=D.F64, device=hit.device)
+    h = torch.empty(n, dtype=D.F64, device=hit.device) if want_height else None
+    fl = torch.zeros(1, dtype=torch.int32, device=hit.device)
+    _lib.check(_lib.lib().akb_figure_displace_f64(fm.desc(hit.device), D.host_f64(coeffs), D.ptr(hit), n, D.ptr(dirs), n, n,
+                                                  D.ptr(out), n, D.ptr(h) if want_height else None, D.ptr(fl),
+                                                  D.stream_handle()))
+    if want_height:
+        return out, int(fl.item()), h
+    return out, int(fl.item())
+
+
+def displace_hits(mirrors, figure, hits, src):
+    """The wave chain's mirror grids with the maps on them: mirror k's materialised hits
+    (3, n) moved by displace() with the incoming direction hits[k] - hits[k - 1] (hits[0] - src for the
+    first mirror; unnormalised, only its sign is used). figure: one FigureMap or None per mirror; src:
+    the source point (3 values, or a (3, 1) / (3, n) tensor). Returns (the list of grids - an unmapped
+    mirror's tensor unchanged -, the flag word with mirror k's bits at 4k)."""
+    import torch
+
+    from . import device as D
+    out, word = [], 0
+    prev = None
+    for k, m in enumerate(mirrors):
+        p = hits[k]
+        f = figure[k]
+        if f is None:
+            out.append(p)
+        else:
+            if prev is None:
+                prev = src if isinstance(src, torch.Tensor) else torch.tensor([float(x) for x in src], dtype=D.F64)
+                prev = prev.to(device=p.device, dtype=D.F64).reshape(3, -1)
+            q, fl = displace(f, m.coeffs, p, p - prev)
+            word |= (fl & (_lib.FLAG_FIG_OUTSIDE | _lib.FLAG_ZERO_NORMAL)) << (4 * k)
+            out.append(q)
+        prev = p
+    return out, word
+
+
+def sampling(fm, grid, n_v, n_h):
+    """How finely a (3, n_v * n_h) grid of sample points (row-major, n_h fastest) samples the map fm: the
+    largest distance between neighbouring samples - along the rows and along the columns - measured
+    along e_u and along e_w, next to the map's pitches. Returns a dict (su, sw, du, dw). Host numpy."""
+    g = np.asarray(grid, dtype=np.float64)[:3].reshape(3, int(n_v), int(n_h))
+    d = g - fm.origin.reshape(3, 1, 1)
+    out = {}
+    for name, e in (("su", fm.e_u), ("sw", fm.e_w)):
+        c = np.tensordot(e, d, axes=(0, 0))
+        steps = [np.abs(np.diff(c, axis=a)) for a in (0, 1) if c.shape[a] > 1]
+        out[name] = float(max((s.max() for s in steps), default=0.0))
+    out["du"], out["dw"] = fm.du, fm.dw
+    return out
 
 
 def stage_normals(mirrors, figure, dirs, src, with_segments=False, prims=None, with_terms=False):

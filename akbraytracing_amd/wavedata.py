@@ -275,8 +275,29 @@ def two_pass_trace(b, n, mode="wave"):
     return r2.hits, r2.dir_out, r2.det
 
 
+def _figure_hits(b, figure, hits):
+    """figure= of the 'wave' modes: the checked list (None without maps) and, per mirror in trace
+    order, the hits of two_pass_trace displaced in lab coordinates (None for a mirror without a map)."""
+    from . import geometry as G
+    from .figure import check_figure, displace_hits, outside_error
+    mir = G.mirrors_of(b)
+    fig = check_figure(figure(b) if callable(figure) else figure, len(mir))
+    if fig is None:
+        return None, None
+    lab = [hits[k] for k in range(len(mir))]
+    moved, word = displace_hits(mir, fig, lab, b["source"])
+    msg = outside_error(word)
+    if msg:
+        raise _lib.AKBError(msg)
+    zero = [k for k in range(len(mir)) if word & (_lib.FLAG_ZERO_NORMAL << (4 * k))]
+    if zero:
+        raise _lib.AKBError("a zero-norm surface normal on mirror " + ", ".join(str(k) for k in zero)
+                            + f" (flags {word:#x}): its samples cannot be displaced along the normal")
+    return fig, [q if f is not None else None for q, f in zip(moved, fig)]
+
+
 def plot_result_wave(params, ray_num, *, defocus_for_wave=1e-3, option_set=True, source_shift=(0.0, 0.0, 0.0),
-                     as_torch=False):
+                     as_torch=False, figure=None, _lab=None):
     """plot_result_debug(params, 'wave') (AKB_raytrace_20250312.py:2675-2905, :3510-3561) on the
     device for the AKB system built from params (geometry.build_akb), on a ray_num x ray_num grid:
     pass 1, the equal-angle resample (host numpy arctan / tan and the C interp1d, as RayWave), pass
@@ -285,7 +306,14 @@ def plot_result_wave(params, ray_num, *, defocus_for_wave=1e-3, option_set=True,
     the re-intersected detector and, when |defocus_for_wave| > 1e-9, the defocused one. Returns the
     reference's tuple: (source, vmirr_hyp, hmirr_hyp, vmirr_ell, hmirr_ell, detcenter[, detcenter2],
     ray_num_H, ray_num_V, vmirr_norm, hmirr_norm, vmirr2_norm, hmirr2_norm, vec0to1, vec1to2,
-    vec2to3, vec3to4), or np.inf where the reference returns np.inf."""
+    vec2to3, vec3to4), or np.inf where the reference returns np.inf.
+
+    figure: one figure.FigureMap or None per mirror in trace order (a list, or a callable built ->
+    list): each mapped mirror's hits are displaced along the normal by the map's height in
+    lab coordinates before the rotation, and only the mirror grids move - the source, the detector
+    grids, the *_norm and vec* arrays are the figure-free run's. A hit outside a map raises AKBError.
+    _lab: a dict that receives the checked figure list and the lab-frame hits (saveWaveData's sampling
+    check)."""
     from . import geometry as G
     from . import primitives as P
     from .reduce import means_to_host, np_sum
@@ -305,6 +333,9 @@ def plot_result_wave(params, ray_num, *, defocus_for_wave=1e-3, option_set=True,
     rot = [P.rotate_points(hits[k], focus, -theta_y, -theta_z) for k in range(4)]
     src_rot = P.rotate_points(source0, focus, -theta_y, -theta_z)
     vmirr_hyp, vmirr_ell, hmirr_ell, hmirr_hyp = rot
+    fig, moved = _figure_hits(b, figure, hits)
+    if _lab is not None:
+        _lab.update(figure=fig, hits=hits)
     detcenter = P.plane_ray_intersection(b["det1"], refl_rot, hmirr_hyp)
     vec0to1 = P.normalize_vector(vmirr_hyp - src_rot)
     vec1to2 = P.normalize_vector(vmirr_ell - vmirr_hyp)
@@ -314,6 +345,9 @@ def plot_result_wave(params, ray_num, *, defocus_for_wave=1e-3, option_set=True,
     norms = [P.normalize_vector((-b_ + a_) / 2) for a_, b_ in
              ((vec0to1, vec1to2), (vec1to2, vec2to3), (vec2to3, vec3to4), (vec3to4, vec4to5))]
     out = [src_rot, vmirr_hyp, hmirr_hyp, vmirr_ell, hmirr_ell, detcenter]
+    if fig is not None:  # only the grids move: the vectors and both detectors keep the undisplaced hits
+        g = [rot[k] if moved[k] is None else P.rotate_points(moved[k], focus, -theta_y, -theta_z) for k in range(4)]
+        out[1:5] = [g[0], g[3], g[1], g[2]]
     if np.abs(defocus_for_wave) > 1e-9:
         c2 = np.zeros(10)
         c2[6] = 1
@@ -326,7 +360,7 @@ def plot_result_wave(params, ray_num, *, defocus_for_wave=1e-3, option_set=True,
 
 
 def kb_wave(params, ray_num, *, defocus_for_wave=1e-3, source_shift=(0.0, 0.0, 0.0), designparams=None,
-            as_torch=False):
+            as_torch=False, figure=None, _lab=None):
     """KB_debug(params, na_ratio_h, na_ratio_v, 'wave') (AKB_raytrace_20250312.py:10948-11054,
     :11629-11701; option_rotate True, option_avrgsplt False) on the device for the KB pair of
     geometry.build_kb on a ray_num x ray_num grid: pass 1, reset_p0's equal-angle resample, pass 2,
@@ -334,7 +368,7 @@ def kb_wave(params, ray_num, *, defocus_for_wave=1e-3, source_shift=(0.0, 0.0, 0
     np.mean(detcenter, axis=1), the re-intersected detector and, when |defocus_for_wave| > 1e-9, the
     defocused one. Returns the reference's tuple: (source, vmirr_hyp, hmirr_hyp, detcenter[,
     detcenter2], ray_num_H, ray_num_V, vmirr_norm, hmirr_norm, vec0to1, vec1to2), or np.inf where
-    the reference returns np.inf."""
+    the reference returns np.inf. figure, _lab: as plot_result_wave (two entries, trace order)."""
     from . import geometry as G
     from . import primitives as P
     from .reduce import means_to_host, np_sum
@@ -359,7 +393,13 @@ def kb_wave(params, ray_num, *, defocus_for_wave=1e-3, source_shift=(0.0, 0.0, 0
     vec2to3 = P.normalize_vector(detcenter - hmirr)
     vmirr_norm = P.normalize_vector((-vec1to2 + vec0to1) / 2)
     hmirr_norm = P.normalize_vector((-vec2to3 + vec1to2) / 2)
+    fig, moved = _figure_hits(b, figure, hits)
+    if _lab is not None:
+        _lab.update(figure=fig, hits=hits)
     out = [src_rot, vmirr, hmirr, detcenter]
+    if fig is not None:  # only the grids move: the vectors and both detectors keep the undisplaced hits
+        out[1:3] = [g if q is None else P.rotate_points(q, focus, -theta_y, -theta_z)
+                    for g, q in zip((vmirr, hmirr), moved)]
     if np.abs(defocus_for_wave) > 1e-9:
         c2 = np.zeros(10)
         c2[6] = 1
@@ -371,9 +411,24 @@ def kb_wave(params, ray_num, *, defocus_for_wave=1e-3, source_shift=(0.0, 0.0, 0
     return tuple(x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in out)
 
 
+def _warn_sampling(k, m, fm, downsampled):
+    """one UserWarning when the samples of mirror k (points_M<m>.npy) are coarser than its map"""
+    import warnings
+
+    from .figure import sampling
+    grid, n_v, n_h = downsampled
+    s = sampling(fm, grid, n_v, n_h)
+    bad = [f"{s[a]:.3e} m along e_{a[1]} against the map's pitch {s['d' + a[1]]:.3e} m"
+           for a, n in (("su", fm.nu), ("sw", fm.nw)) if n > 1 and s[a] > s["d" + a[1]]]
+    if bad:
+        warnings.warn(f"mirror {k} (points_M{m}.npy): neighbouring samples lie " + " and ".join(bad)
+                      + ": the Huygens sum sees the figure map aliased", UserWarning, stacklevel=3)
+
+
 def saveWaveData(initial_params, ysize=1e-6, zsize=1e-6, *, ray_num_H=65, ray_num_V=None, directory=None,
                  defocus_for_wave=1e-3, downsample=(0, 0, 0, 0, 0, 0), option_set=True, option_HighNA=True,
-                 option_2mirror=True, option_avrgsplt=False, timestamp=None, option_AKB=True, kb_design=None):
+                 option_2mirror=True, option_avrgsplt=False, timestamp=None, option_AKB=True, kb_design=None,
+                 figure=None):
     """saveWaveData (AKB_raytrace_20250312.py:13475-13764) for the AKB system, without its final
     sys.exit(): the 'wave' run (plot_result_wave), downsample_array_3_n of every grid when the grid
     is odd (:13489-13497, factors (h1, v1, h2, v2, h_f, v_f) = the module's downsample_* flags), the
@@ -381,16 +436,24 @@ def saveWaveData(initial_params, ysize=1e-6, zsize=1e-6, *, ray_num_H=65, ray_nu
     as the reference). Returns the directory. The module flags the reference reads (wave_num_H /
     wave_num_V, defocusForWave, option_HighNA, option_2mirror, option_avrgsplt, option_set) are
     keyword arguments here; install() passes the module's live values. option_AKB False: KB_debug's
-    pair (kb_wave; kb_design = the module's KBdesign_7params) and its two-mirror file set."""
+    pair (kb_wave; kb_design = the module's KBdesign_7params) and its two-mirror file set.
+
+    figure: as plot_result_wave - the mapped mirrors' points_M<k>.npy hold the displaced grids and
+    calc_dS of them, every other file is the figure-free run's. A mapped mirror whose (downsampled)
+    samples lie further apart than the map's pitch draws a UserWarning: the Huygens sum then sees the
+    map aliased."""
     from datetime import datetime
     ray_num_V = ray_num_H if ray_num_V is None else ray_num_V
     if ray_num_V != ray_num_H:
         raise ValueError("the 'wave' grid is square (ray_num = wave_num_H, :1890-1893, :10412-10415)")
     two = np.abs(defocus_for_wave) > 1e-9
+    lab = {}
     if option_AKB:
-        r = plot_result_wave(initial_params, ray_num_H, defocus_for_wave=defocus_for_wave, option_set=option_set)
+        r = plot_result_wave(initial_params, ray_num_H, defocus_for_wave=defocus_for_wave, option_set=option_set,
+                             figure=figure, _lab=lab)
     else:
-        r = kb_wave(initial_params, ray_num_H, defocus_for_wave=defocus_for_wave, designparams=kb_design)
+        r = kb_wave(initial_params, ray_num_H, defocus_for_wave=defocus_for_wave, designparams=kb_design,
+                    figure=figure, _lab=lab)
     if not isinstance(r, tuple):
         raise TypeError("cannot unpack non-iterable float object")  # the reference unpacks np.inf
     if option_AKB:
@@ -404,6 +467,12 @@ def saveWaveData(initial_params, ysize=1e-6, zsize=1e-6, *, ray_num_H=65, ray_nu
         # the reference only sets the grid sizes inside its odd-grid branch
         raise NameError("name 'size_v1' is not defined")
     h1, v1, h2, v2, hf, vf = downsample
+    if lab.get("figure") is not None:
+        # per mirror in trace order: its file and its downsample factors
+        files = ((1, h1, v1), (3, h1, v1), (4, h2, v2), (2, h2, v2)) if option_AKB else ((1, h1, v1), (2, h2, v2))
+        for k, (fm, (m, dh, dv)) in enumerate(zip(lab["figure"], files)):
+            if fm is not None:
+                _warn_sampling(k, m, fm, downsample_array_3_n(_host(lab["hits"][k]), ray_num_V, ray_num_H, dh, dv))
     vmirr_hyp, size_v1, size_h1 = downsample_array_3_n(vmirr_hyp, ray_num_V, ray_num_H, h1, v1)
     hmirr_hyp, size_v2, size_h2 = downsample_array_3_n(hmirr_hyp, ray_num_V, ray_num_H, h2, v2)
     detcenter, size_v_f, size_h_f = downsample_array_3_n(detcenter, ray_num_V, ray_num_H, hf, vf)

@@ -28,6 +28,9 @@
  *   akb_figure_normal_f64 (no reference call: the same map's slope turning the normal the reflection
  *                        uses - slope error in the ray-spot modes; akb_chain_desc.fig_slope fuses it
  *                        into akb_trace_chain_f64 and akb_trace_chain_batch_f64)
+ *   akb_figure_displace_f64 (no reference call: the same map moving the mirror's sample points along
+ *                        the normal - figure error in the points_M<k>.npy set saveWaveData writes and
+ *                        the Wavecalc chain propagates)
  *   akb_trace_chain_f64  the pass-1 / pass-2 mirror chains of plot_result_debug
  *                        AKB_raytrace_20250312.py:2694-2717 (ray grid), :2770-2845 (pass 1),
  *                        :2881-2905 (pass 2 + OPL segments); KB_debug :10952-10997
@@ -159,6 +162,20 @@ int akb_figure_opl_f64(const akb_figure_map* map, const double coeffs[10], const
 int akb_figure_normal_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
                           const double* dir, int64_t dir_ld, int64_t n, double* normal_out, int64_t normal_ld,
                           int32_t* flags, void* stream);
+
+/* One mirror's displaced sample points for n hits (3, hit_ld) with incoming directions (3, dir_ld):
+ * with N the quadric's unit normal at the hit (akb_normal_f64's expressions), h the map's Catmull-Rom
+ * interpolation there and sigma = (dir . N > 0) ? -1 : 1,
+ *     P' = P + (sigma h) N
+ * (positive h is a bump towards the incoming beam; only the sign of dir . N is read, so dir need not be
+ * unit). out (3, out_ld) receives P', h_out (n, or NULL) the interpolated height. A hit outside the map
+ * gives P itself bit for bit and h = +0 and ORs AKB_FLAG_FIG_OUTSIDE into *flags; a NaN hit gives NaN
+ * and no flag; a zero-norm normal ORs AKB_FLAG_ZERO_NORMAL and that sample's out is P. out overlapping
+ * hit or dir is refused (AKB_E_INVALID); h_out must not overlap them either. The mirror grids of the
+ * wave chain's file set (points_M<k>.npy) are these points. */
+int akb_figure_displace_f64(const akb_figure_map* map, const double coeffs[10], const double* hit, int64_t hit_ld,
+                            const double* dir, int64_t dir_ld, int64_t n, double* out, int64_t out_ld,
+                            double* h_out /* (n) or NULL */, int32_t* flags, void* stream);
 
 /* normalize_vector: out = v / ||v|| ; ORs AKB_FLAG_ZERO_DIR if any ||v|| == 0 (caller keeps v). */
 int akb_normalize_f64(const double* v, int64_t v_ld, int64_t v_inc, int64_t n, double* out,
