@@ -33,9 +33,12 @@ constexpr int kTPL = AKB_HUY_TPL;  // targets per lane
 
 // Pair distance and half its reciprocal from one rsq: r = sqrt(x) correctly rounded (sqrt_core's
 // sequence, akb_common.h, exact for x in [2^-767, 2^1000] - every distance between points metres
-// apart) and h ~ 0.5 / r after one Newton step (relative error ~1e-13, one-signed; the factor 2 is
-// applied to the sums once at the end, exactly). x = 0 (a target on a source, where the
-// reference's amplitude is inf too) gives r = 0.
+// apart) and h ~ 0.5 / r after one Newton step (relative error ~1e-13 promised, one-signed; measured
+// <= 4.3e-15 on the MI355X, DESIGN.md section 3, "Huygens per-pair bars"; the factor 2 is
+// applied to the sums once at the end, exactly). x = 0 (a target on a source) gives r = 0 and
+// h = NaN (rsq(0) = inf, then 0 * inf in the Newton step), so that target's sum is NaN in both
+// parts - as numpy's is: (1 / 0) * exp(i 0) = inf + nan i, NaN in both parts once it is multiplied
+// by the source's field. x = inf or NaN gives r = h = NaN.
 __device__ __forceinline__ void dist_half_inv(double x, double& r, double& h) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
