@@ -188,6 +188,127 @@ __global__ void __launch_bounds__(kHuyBlock) k_huygens(const double* __restrict_
     }
 }
 
+// Several fields over one geometry (an extended source's mutually incoherent points, DESIGN.md
+// section 7.7): the distance, its sqrt, the phase reduction and the two polynomials depend on the
+// points and k alone, so one pass forms fr = amp cos, fi = amp sin per pair once and spends four
+// FMAs per field on it. Row f of the result is k_huygens' for u[f] alone, bit for bit: the same
+// fr / fi (pair_factor repeats pair_add's operations), the same two FMA chains per target in the
+// same source order inside a split, nothing contracted or reassociated.
+template <bool kSlow>
+__device__ __forceinline__ bool pair_factor(double px, double py, double pz, double xj, double yj, double zj,
+                                            double negk, double& fr, double& fi) {
+    const double dx = px - xj;
+    const double dy = py - yj;
+    const double dz = pz - zj;
+    double r, amp;  // amp = 1 / (2 r)
+    dist_half_inv(dx * dx + dy * dy + dz * dz, r, amp);
+    const double ph = negk * r;
+    double sn, cs;
+    bool ok = true;
+    if (kSlow) sincos_slow(ph, sn, cs);
+    else ok = sincos_phase_fast(ph, sn, cs);
+    fr = amp * cs;
+    fi = amp * sn;
+    return ok;
+}
+
+// kF fields per pass. u: kF rows of m interleaved complex128, `urow` doubles apart (2 m); out: one
+// split's partials are (kF, 2 n) contiguous, so k_huygens_reduce runs over cols = 2 n kF. The LDS
+// tile holds a source's kF fields side by side (re, im, re, im, ...): every lane reads the same
+// address (a broadcast, no bank conflict) and a field's pair comes in one 128-bit read.
+template <int kF>
+__global__ void __launch_bounds__(kHuyBlock) k_huygens_fields(const double* __restrict__ tx,
+                                                              const double* __restrict__ ty,
+                                                              const double* __restrict__ tz, int64_t n,
+                                                              const double* __restrict__ sx,
+                                                              const double* __restrict__ sy,
+                                                              const double* __restrict__ sz,
+                                                              const double* __restrict__ u, int64_t urow,
+                                                              int64_t m, int64_t per_split, double negk,
+                                                              double* __restrict__ out) {
+    __shared__ double s_x[kHuyTile], s_y[kHuyTile], s_z[kHuyTile];
+    __shared__ double2 s_u[kHuyTile * kF];
+    const int64_t base = (int64_t)blockIdx.x * (kHuyBlock * kTPL);
+    double px[kTPL], py[kTPL], pz[kTPL], ar[kTPL][kF], ai[kTPL][kF];
+#pragma unroll
+    for (int t = 0; t < kTPL; ++t) {
+        const int64_t i = base + threadIdx.x + t * kHuyBlock;
+        const bool ok = i < n;
+        // a lane's slots past the last target sit at the origin: finite pairs, sums never written
+        px[t] = ok ? tx[i] : 0.0;
+        py[t] = ok ? ty[i] : 0.0;
+        pz[t] = ok ? tz[i] : 0.0;
+#pragma unroll
+        for (int f = 0; f < kF; ++f) ar[t][f] = ai[t][f] = 0.0;
+    }
+    const int64_t jb = (int64_t)blockIdx.y * per_split;
+    const int64_t je = (jb + per_split) < m ? (jb + per_split) : m;
+    out += (int64_t)blockIdx.y * 2 * n * kF;
+    bool fast[kTPL];  // every pair of target t stayed in the fast phase range
+#pragma unroll
+    for (int t = 0; t < kTPL; ++t) fast[t] = true;
+    for (int64_t j0 = jb; j0 < je; j0 += kHuyTile) {
+        const int cnt = (je - j0) < kHuyTile ? (int)(je - j0) : kHuyTile;
+        __syncthreads();
+        for (int s = threadIdx.x; s < cnt; s += kHuyBlock) {
+            const int64_t j = j0 + s;
+            s_x[s] = sx[j];
+            s_y[s] = sy[j];
+            s_z[s] = sz[j];
+#pragma unroll
+            for (int f = 0; f < kF; ++f)
+                s_u[s * kF + f] = make_double2(u[f * urow + 2 * j], u[f * urow + 2 * j + 1]);
+        }
+        __syncthreads();
+        for (int s = 0; s < cnt; ++s) {
+            const double xj = s_x[s], yj = s_y[s], zj = s_z[s];
+            double fr[kTPL], fi[kTPL];
+#pragma unroll
+            for (int t = 0; t < kTPL; ++t)
+                fast[t] &= pair_factor<false>(px[t], py[t], pz[t], xj, yj, zj, negk, fr[t], fi[t]);
+#pragma unroll
+            for (int f = 0; f < kF; ++f) {
+                const double2 w = s_u[s * kF + f];
+#pragma unroll
+                for (int t = 0; t < kTPL; ++t) {
+                    ar[t][f] = __builtin_fma(fr[t], w.x, __builtin_fma(-fi[t], w.y, ar[t][f]));
+                    ai[t][f] = __builtin_fma(fr[t], w.y, __builtin_fma(fi[t], w.x, ai[t][f]));
+                }
+            }
+        }
+    }
+    // the fix-up of k_huygens, for every field of the group: outside the pair loop, one library
+    // sincos per pair
+#pragma unroll
+    for (int t = 0; t < kTPL; ++t) {
+        if (__builtin_expect(!fast[t], 0)) {
+#pragma unroll
+            for (int f = 0; f < kF; ++f) ar[t][f] = ai[t][f] = 0.0;
+            for (int64_t j = jb; j < je; ++j) {
+                double fr, fi;
+                pair_factor<true>(px[t], py[t], pz[t], sx[j], sy[j], sz[j], negk, fr, fi);
+#pragma unroll
+                for (int f = 0; f < kF; ++f) {
+                    const double ur = u[f * urow + 2 * j], ui = u[f * urow + 2 * j + 1];
+                    ar[t][f] = __builtin_fma(fr, ur, __builtin_fma(-fi, ui, ar[t][f]));
+                    ai[t][f] = __builtin_fma(fr, ui, __builtin_fma(fi, ur, ai[t][f]));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < kTPL; ++t) {
+        const int64_t i = base + threadIdx.x + t * kHuyBlock;
+        if (i < n) {
+#pragma unroll
+            for (int f = 0; f < kF; ++f) {
+                out[(int64_t)f * 2 * n + 2 * i] = 2.0 * ar[t][f];  // the 1 / (2 r) amplitudes' factor 2, exact
+                out[(int64_t)f * 2 * n + 2 * i + 1] = 2.0 * ai[t][f];
+            }
+        }
+    }
+}
+
 // out = sum over splits of the partial fields, in two ordered levels over the 2n interleaved
 // doubles (cols): chunks of kRedChunk consecutive splits, then the chunks in order. Each split
 // row is read by consecutive lanes. (One lane per target summing all splits kept 4225 lanes busy
@@ -272,6 +393,17 @@ static int64_t huygens_work_bytes(int64_t n, int splits) {
     return ((int64_t)splits + (chunks > 1 ? chunks : 0)) * 2 * n * (int64_t)sizeof(double);
 }
 
+// fields per pass of akb_huygens_fields_f64 (4 or 8); a remainder takes the instantiation of its
+// own size, a single field k_huygens. 8 from the measurement (MI355X, profiles/r08a_huygens_fields.json,
+// ms per field, single calls / 4 per pass / 8 per pass): n = 4225, m = 1e7: 84.8 / 25.7 / 16.2;
+// n = 65536, m = 1e6: 121.8 / 37.0 / 23.3 - a pass of 8 costs 1.53 single passes at 3 waves a SIMD,
+// a pass of 4 costs 1.21 at 4.
+#ifndef AKB_HUY_GROUP
+#define AKB_HUY_GROUP 8
+#endif
+constexpr int kHuyGroup = AKB_HUY_GROUP;
+static_assert(kHuyGroup == 4 || kHuyGroup == 8, "AKB_HUY_GROUP is 4 or 8");
+
 extern "C" {
 
 int akb_huygens_splits(int64_t n, int64_t m) { return n > 0 && m > 0 ? huygens_splits(n, m) : 1; }
@@ -315,6 +447,77 @@ int akb_huygens_f64(const double* tx, const double* ty, const double* tz, int64_
     if ((st = launch_status("k_huygens_reduce")) || chunks == 1) return st;
     k_huygens_reduce<<<dim3(bx, 1), kBlock, 0, s>>>(lvl, chunks, chunks, cols, out_re_im);
     return launch_status("k_huygens_reduce");
+}
+
+int64_t akb_huygens_fields_work_bytes(int64_t n, int64_t m, int splits, int nf) {
+    if (n <= 0 || m <= 0 || nf < 1) return 0;
+    const int64_t one = huygens_work_bytes(n, splits > 0 ? splits : huygens_splits(n, m));
+    return one * (nf < kHuyGroup ? nf : kHuyGroup);
+}
+
+int akb_huygens_fields_f64(const double* tx, const double* ty, const double* tz, int64_t n,
+                           const double* sx, const double* sy, const double* sz, const double* u_re_im,
+                           int64_t m, int nf, double k, double* out_re_im, int splits, void* work,
+                           void* stream) {
+    clear_error();
+    AKB_REQUIRE(n >= 0 && m >= 0, "negative size");
+    AKB_REQUIRE(nf >= 1, "at least one field");
+    if (n == 0) return AKB_OK;
+    AKB_REQUIRE(tx && ty && tz && out_re_im, "null target pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        AKB_HIP_CHECK(hipMemsetAsync(out_re_im, 0, sizeof(double) * 2 * n * nf, s));
+        return AKB_OK;
+    }
+    AKB_REQUIRE(sx && sy && sz && u_re_im, "null source pointer");
+    const int64_t per_block = (int64_t)kHuyBlock * kTPL;
+    const int64_t blocks = (n + per_block - 1) / per_block;
+    AKB_REQUIRE(blocks < (1LL << 31) / kHuyGroup, "too many targets");  // (the reduce's grid over 2 n g columns)
+    if (splits <= 0) splits = huygens_splits(n, m);  // the single-field call's count, not this kernel's
+    AKB_REQUIRE(splits <= 65535, "at most 65535 source splits");
+    AKB_REQUIRE(splits == 1 || work != nullptr, "work buffer required (akb_huygens_fields_work_bytes)");
+    const int64_t per_split = (m + splits - 1) / splits;
+    const int chunks = (splits + kRedChunk - 1) / kRedChunk;
+    const dim3 grid((unsigned)blocks, splits);
+    // the groups run one after another on the stream, through the same work buffer
+    for (int f0 = 0; f0 < nf;) {
+        const int g = (nf - f0) < kHuyGroup ? (nf - f0) : kHuyGroup;
+        const double* u = u_re_im + (int64_t)f0 * 2 * m;
+        double* out = out_re_im + (int64_t)f0 * 2 * n;
+        double* dst = splits == 1 ? out : (double*)work;
+        switch (g) {
+            case 1: k_huygens<<<grid, kHuyBlock, 0, s>>>(tx, ty, tz, n, sx, sy, sz, u, m, per_split, -k, dst); break;
+#define AKB_HUY_FIELDS(F)                                                                                    \
+    case F: k_huygens_fields<F><<<grid, kHuyBlock, 0, s>>>(tx, ty, tz, n, sx, sy, sz, u, 2 * m, m, per_split, \
+                                                           -k, dst); break;
+            AKB_HUY_FIELDS(2)
+            AKB_HUY_FIELDS(3)
+            AKB_HUY_FIELDS(4)
+#if AKB_HUY_GROUP == 8
+            AKB_HUY_FIELDS(5)
+            AKB_HUY_FIELDS(6)
+            AKB_HUY_FIELDS(7)
+            AKB_HUY_FIELDS(8)
+#endif
+#undef AKB_HUY_FIELDS
+            default: AKB_REQUIRE(false, "no kernel for this group of fields");
+        }
+        int st = launch_status("k_huygens_fields");
+        if (st) return st;
+        if (splits > 1) {
+            const int64_t cols = 2 * n * g;
+            const unsigned bx = (unsigned)((cols + kBlock - 1) / kBlock);
+            double* lvl = chunks > 1 ? dst + (int64_t)splits * cols : out;  // chunk sums after the partials
+            k_huygens_reduce<<<dim3(bx, (unsigned)chunks), kBlock, 0, s>>>(dst, splits, kRedChunk, cols, lvl);
+            if ((st = launch_status("k_huygens_reduce"))) return st;
+            if (chunks > 1) {
+                k_huygens_reduce<<<dim3(bx, 1), kBlock, 0, s>>>(lvl, chunks, chunks, cols, out);
+                if ((st = launch_status("k_huygens_reduce"))) return st;
+            }
+        }
+        f0 += g;
+    }
+    return AKB_OK;
 }
 
 int akb_scale_field_f64(const double* u_re_im, const double* ds, int64_t m, double* out_re_im,

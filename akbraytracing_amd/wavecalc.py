@@ -41,6 +41,20 @@ def splits_for(n, m):
     return int(_lib.lib().akb_huygens_splits(int(n), int(m)))
 
 
+def _work_for(work, need, dev, stream):
+    """work when it holds need bytes, else this thread's cached buffer for (device, stream), grown
+    to need."""
+    if need > 0 and (work is None or work.numel() * 8 < need):
+        # keyed by (device, stream): calls on two streams of one thread may overlap on the device,
+        # so they must not share the split partials
+        cache = _WORK.__dict__.setdefault("by_stream", {})
+        key = (dev, D.stream_handle(stream).value)
+        work = cache.get(key)
+        if work is None or work.numel() * 8 < need:
+            work = cache[key] = torch.empty(need // 8 + 1, dtype=D.F64, device=dev)
+    return work
+
+
 def propagate(tx, ty, tz, sx, sy, sz, u_ds, k, stream=None, work=None, splits=0):
     """Device API: all arguments float64 / complex128 device tensors (u_ds already times dS).
     splits: the source-split count (0: the library's for these sizes; a target-sharded caller
@@ -51,18 +65,42 @@ def propagate(tx, ty, tz, sx, sy, sz, u_ds, k, stream=None, work=None, splits=0)
     n, m = int(tx.shape[0]), int(sx.shape[0])
     out = torch.empty(n, dtype=torch.complex128, device=dev)
     need = int(L.akb_huygens_work_bytes(n, m, int(splits)))
-    if need > 0 and (work is None or work.numel() * 8 < need):
-        # keyed by (device, stream): calls on two streams of one thread may overlap on the device,
-        # so they must not share the split partials
-        cache = _WORK.__dict__.setdefault("by_stream", {})
-        key = (dev, D.stream_handle(stream).value)
-        work = cache.get(key)
-        if work is None or work.numel() * 8 < need:
-            work = cache[key] = torch.empty(need // 8 + 1, dtype=D.F64, device=dev)
+    work = _work_for(work, need, dev, stream)
     ur = torch.view_as_real(u_ds)
     _lib.check(L.akb_huygens_f64(D.ptr(tx), D.ptr(ty), D.ptr(tz), n, D.ptr(sx), D.ptr(sy), D.ptr(sz), D.ptr(ur), m,
                                  float(k), D.ptr(torch.view_as_real(out)), int(splits),
                                  D.ptr(work) if need > 0 else None, D.stream_handle(stream)))
+    return out
+
+
+def fields_per_pass():
+    """The most fields one pass of akb_huygens_fields_f64 carries (the library's group size), read
+    off its work-size rule: min(nf, group) times the single-field figure."""
+    L = _lib.lib()
+    return int(L.akb_huygens_fields_work_bytes(1, 1, 2, 1 << 20)) // int(L.akb_huygens_work_bytes(1, 1, 2))
+
+
+def propagate_fields(tx, ty, tz, sx, sy, sz, U_ds, k, stream=None, work=None, splits=0):
+    """propagate for F fields over one geometry in shared passes (akb_huygens_fields_f64): U_ds is
+    an (F, m) complex128 device tensor, every row already times dS; returns the (F, n) complex128
+    device tensor whose row f is propagate(..., U_ds[f], ...) with the same splits, bit for bit.
+    A 1-D U_ds is refused (propagate is for that)."""
+    if U_ds.dim() != 2:
+        raise ValueError(f"U_ds must be (F, m), got {tuple(U_ds.shape)}: propagate takes a single field")
+    n, m, nf = int(tx.shape[0]), int(sx.shape[0]), int(U_ds.shape[0])
+    if nf < 1 or int(U_ds.shape[1]) != m:
+        raise ValueError(f"U_ds {tuple(U_ds.shape)} does not hold one or more fields over {m} sources")
+    if U_ds.dtype != torch.complex128:
+        raise ValueError(f"U_ds must be complex128, got {U_ds.dtype}")
+    L = _lib.lib()
+    dev = tx.device
+    out = torch.empty((nf, n), dtype=torch.complex128, device=dev)
+    need = int(L.akb_huygens_fields_work_bytes(n, m, int(splits), nf))
+    work = _work_for(work, need, dev, stream)
+    ur = torch.view_as_real(U_ds.contiguous())
+    _lib.check(L.akb_huygens_fields_f64(D.ptr(tx), D.ptr(ty), D.ptr(tz), n, D.ptr(sx), D.ptr(sy), D.ptr(sz), D.ptr(ur),
+                                        m, nf, float(k), D.ptr(torch.view_as_real(out)), int(splits),
+                                        D.ptr(work) if need > 0 else None, D.stream_handle(stream)))
     return out
 
 

@@ -164,9 +164,127 @@ def load_npz_data(filename):
     return None
 
 
+def source_grid(centre, size_y, size_z, ny, nz, profile="gaussian"):
+    """An extended, spatially incoherent source as ny x nz point emitters (host only): the points
+    (3, S) in y and z about centre at centre's x (the chain's axis is x, as in image_grid) and their
+    weights (S,), normalised to sum 1. profile "uniform": the grid spans +-size / 2 with equal
+    weights; "gaussian": size_* is the FWHM, the grid spans +-1.5 FWHM and the weights are the
+    Gaussian's values at the points. ny or nz equal to 1 collapses that axis onto the centre."""
+    if profile not in ("gaussian", "uniform"):
+        raise ValueError(f"profile is 'gaussian' or 'uniform', not {profile!r}")
+    c = np.asarray(centre, dtype=np.float64).reshape(-1)
+    ny, nz = int(ny), int(nz)
+    if c.shape != (3,) or ny < 1 or nz < 1 or not (size_y >= 0 and size_z >= 0):
+        raise ValueError("source_grid takes a centre of 3 coordinates, sizes >= 0 and counts >= 1")
+
+    def axis(size, count):
+        half = 1.5 * size if profile == "gaussian" else 0.5 * size
+        # (i - (count - 1) / 2) * pitch: antisymmetric about the centre to the bit
+        off = (np.arange(count) - (count - 1) / 2) * (2 * half / (count - 1)) if count > 1 else np.zeros(1)
+        if profile == "uniform" or count == 1 or size == 0:
+            return off, np.ones(count)
+        sigma = size / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+        return off, np.exp(-0.5 * (off / sigma) ** 2)
+
+    (oy, wy), (oz, wz) = axis(float(size_y), ny), axis(float(size_z), nz)
+    yy, zz = np.meshgrid(c[1] + oy, c[2] + oz)
+    w = (wz[:, None] * wy[None, :]).flatten()
+    points = np.vstack([np.full(ny * nz, c[0]), yy.flatten(), zz.flatten()])
+    return points, w / np.sum(w)
+
+
+def _check_sources(sources, weights):
+    """(points (3, S) float64, weights (S,) float64) of run_wave_chain's extended source, or
+    ValueError; host only."""
+    p = np.array(_host(sources), dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] != 3:
+        raise ValueError(f"sources must be (3, S), got {p.shape}")
+    S = p.shape[1]
+    if S == 0:
+        raise ValueError("sources holds no point")
+    if not np.all(np.isfinite(p)):
+        raise ValueError("sources holds a non-finite coordinate")
+    if weights is None:
+        w = np.full(S, 1.0 / S)
+    else:
+        w = np.array(_host(weights), dtype=np.float64)
+        if w.shape != (S,):
+            raise ValueError(f"weights must be ({S},) for {S} source points, got {w.shape}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("weights holds a non-finite value")
+    return p, w
+
+
+def _run_wave_chain_sources(folder, out_dir, files, resume_dir, resumed, sources, weights):
+    """run_wave_chain for an extended source: S mutually incoherent unit
+    point emitters. The first stage runs per point (one source each, as the single-source chain's);
+    every later stage is one propagate_fields call over the S fields. Row s of every field is the
+    single-source chain's with points_source.npy = sources[:, s], bit for bit."""
+    from .wavecalc import propagate, propagate_fields, scale_field
+    cond = read_conditions(folder)
+    akb = cond.get("option_AKB", True)
+    wl = np.float64(13.5e-9 if cond.get("option_HighNA", True) else 13.5e-9 * 1e-1)
+    k = 2.0 * np.pi / wl
+    load = lambda name: np.load(os.path.join(folder, name))  # noqa: E731
+    S = sources.shape[1]
+    dev = D.device()
+    fields = {}
+
+    def store(name, u):
+        fields[name] = u.cpu().numpy()
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            np.savez_compressed(os.path.join(out_dir, f"complex_data_{name}.npz"), data=fields[name])
+
+    def scaled(U, ds):
+        return torch.stack([scale_field(U[s], ds) for s in range(S)])
+
+    chain = ["points_M1.npy", "points_M2.npy"] + (["points_M3.npy", "points_M4.npy"] if akb else [])
+    resumed = [] if resumed is None else resumed
+    prev = None  # (x, y, z, ds) of the previous surface on the device
+    U = None     # its (S, N) fields
+    for j, fname in enumerate(chain):
+        pts = load(fname)
+        N = pts.shape[1]
+        tx, ty, tz, ds = (D.to_dev(pts[r, :], dev) for r in range(4))
+        data = load_npz_data(os.path.join(resume_dir, f"complex_data_M{j + 1}.npz")) if resume_dir is not None else None
+        if data is not None:
+            if data.shape != (S, N):
+                raise ValueError(f"complex_data_M{j + 1}.npz holds {data.shape} values for {S} source points "
+                                 f"on {N} points")
+            fields[f"M{j + 1}"] = np.asarray(data, dtype=np.complex128)
+            U = torch.from_numpy(np.ascontiguousarray(fields[f"M{j + 1}"])).to(dev)
+            resumed.append(f"M{j + 1}")
+        else:
+            if j == 0:
+                one = scale_field(torch.ones(1, dtype=torch.complex128, device=dev), torch.ones(1, dtype=D.F64, device=dev))
+                src = D.to_dev(sources, dev)
+                U = torch.stack([propagate(tx, ty, tz, src[0, s:s + 1], src[1, s:s + 1], src[2, s:s + 1], one, k)
+                                 for s in range(S)])
+            else:
+                U = propagate_fields(tx, ty, tz, *prev[:3], scaled(U, prev[3]), k)
+            store(f"M{j + 1}", U)
+        prev = (tx, ty, tz, ds)
+    Uds = scaled(U, prev[3])
+    for name, fname, factor in (("Image", files[3], 2.), ("Image2", files[4], None)):
+        if name == "Image2" and not os.path.exists(os.path.join(folder, fname)):
+            continue
+        img = load(fname).copy()
+        mean = [np.mean(img[0, :]), np.mean(img[1, :]), np.mean(img[2, :])]
+        for r in range(3):  # the driver's arithmetic on both grids (x2 about the mean, and x1)
+            img[r, :] = (img[r, :] - mean[r]) * factor + mean[r] if factor else (img[r, :] - mean[r]) + mean[r]
+        g = [D.to_dev(np.array(img[r, :], dtype=np.float64), dev) for r in range(3)]
+        store(name, propagate_fields(*g, *prev[:3], Uds, k))
+        u = fields[name]
+        fields[f"{name}_intensity"] = (weights[:, None] * (u.real**2 + u.imag**2)).sum(axis=0)
+        if out_dir is not None:
+            np.save(os.path.join(out_dir, f"intensity_{name}.npy"), fields[f"{name}_intensity"])
+    return fields
+
+
 def run_wave_chain(folder, out_dir=None, files=("points_source.npy", "points_M1.npy", "points_M2.npy",
                                                 "points_gridImage.npy", "points_gridDefocus.npy"), resume_dir=".",
-                   resumed=None):
+                   resumed=None, sources=None, weights=None):
     """The Wavecalc_raytrace_fromData driver (CPU0402.py:186-380) on the device: source -> M1 ->
     M2 (-> M3 -> M4) -> image grid (scaled x2 about its mean) and the second image grid, saving
     complex_data_<name>.npz (key 'data') into out_dir. Returns {name: field (numpy complex128)}.
@@ -175,7 +293,20 @@ def run_wave_chain(folder, out_dir=None, files=("points_source.npy", "points_M1.
     complex_data_M<k>.npz is found in resume_dir (the driver looks in the working directory, the
     default here) takes that field instead of propagating, and it is not written again; None
     switches resuming off (resumed, a list, receives the names of the stages taken from files). The
-    image stages are always computed."""
+    image stages are always computed.
+
+    sources (3, S), weights (S,) (default 1 / S each; source_grid makes both): an extended,
+    spatially incoherent source. The points replace points_source.npy, each a unit point emitter
+    incoherent with the others; every field is (S, N), row s the single-source chain's for point s
+    bit for bit, the files hold the (S, N) arrays (a resumed mirror file must be (S, N)), and
+    fields["Image_intensity"] / ["Image2_intensity"] (float64, also saved as intensity_<name>.npy)
+    are (w[:, None] * (u.real**2 + u.imag**2)).sum(axis=0). The mirror files stay the surfaces'
+    quadrature nodes: offsets must be small against the footprint."""
+    if sources is not None or weights is not None:
+        if sources is None:
+            raise ValueError("weights without sources")
+        p, w = _check_sources(sources, weights)
+        return _run_wave_chain_sources(folder, out_dir, files, resume_dir, resumed, p, w)
     from .wavecalc import WaveField3D
     cond = read_conditions(folder)
     akb = cond.get("option_AKB", True)

@@ -495,6 +495,21 @@ int64_t akb_huygens_work_bytes(int64_t n, int64_t m, int splits);
 int akb_huygens_f64(const double* tx, const double* ty, const double* tz, int64_t n,
                     const double* sx, const double* sy, const double* sz, const double* u_re_im,
                     int64_t m, double k, double* out_re_im, int splits, void* work, void* stream);
+/* The same sum for nf fields over one geometry (an extended source's mutually incoherent points,
+ * ref CPU0402 :71-85 once per field): out[f][i] = sum_j u[f][j] * exp(-i k r_ij) / r_ij.
+ * u_re_im: (nf, m) interleaved complex128, rows contiguous, each already multiplied by dS;
+ * out_re_im: (nf, n), laid out the same way. Row f is, bit for bit, what akb_huygens_f64 returns
+ * for u[f] alone with the same split count, for every n, m, nf and splits (NaN and inf included).
+ * splits = 0 is akb_huygens_splits(n, m), the single-field call's count. The fields are walked in
+ * groups of at most 8 per pass, one after another on the stream through the same work buffer.
+ * work: akb_huygens_fields_work_bytes(n, m, splits, nf) bytes = min(nf, 8) times
+ * akb_huygens_work_bytes(n, m, splits), at most ~8 x 516 MiB for the library's count (0 bytes for
+ * one split); concurrent calls need their own. */
+int64_t akb_huygens_fields_work_bytes(int64_t n, int64_t m, int splits, int nf);
+int akb_huygens_fields_f64(const double* tx, const double* ty, const double* tz, int64_t n,
+                           const double* sx, const double* sy, const double* sz, const double* u_re_im,
+                           int64_t m, int nf, double k, double* out_re_im, int splits, void* work,
+                           void* stream);
 /* u_out = u_in * ds (complex * real, ref CPU0402 :102 / GPU0402 :142) */
 int akb_scale_field_f64(const double* u_re_im, const double* ds, int64_t m, double* out_re_im,
                         void* stream);
