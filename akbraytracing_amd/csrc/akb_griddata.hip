@@ -1980,7 +1980,12 @@ __global__ void __launch_bounds__(1024) k_gd_cone_patch(Grid g, ConePatch a, int
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (t == 0) sori[s1 ^ 1] = 0u;  // cell p + 1's word (cell p - 1's was read in its own setup)
+        // cell p's word cleared for cell p + 2: its readers, this step's fresh threads, read it in the
+        // setup above, before the barrier just passed, and its next writers are step p + 2's atomicOrs,
+        // which lie behind step p + 1's first barrier (thread 0 stores this before it arrives there)
+        // whatever Q is. Clearing the other word here, cell p + 1's, races with step p + 1's atomicOrs
+        // when Q == 0 (K <= 2): no barrier of the sweep loop falls between. Both words start at zero.
+        if (t == 0) sori[s1] = 0u;
         if (clk) {
             c1 = wall_clock64();
             c_setup += c1 - c0;

@@ -243,7 +243,7 @@ class CubicGrid:
             # remain (the host checks once per batch; a batch overshoots by at most one sweep then)
             hist.extend(ch.tolist())
             batch = check_every
-            if adaptive and len(hist) >= 4 and hist[-1] > 0 and hist[-4] > hist[-1]:
+            if adaptive and tol > 0 and len(hist) >= 4 and hist[-1] > 0 and hist[-4] > hist[-1]:  # (tol 0: no estimate)
                 rate = (hist[-1] / hist[-4]) ** (1.0 / 3.0)
                 need = int(np.ceil(np.log(tol / hist[-1]) / np.log(rate)))
                 batch = int(min(max(need, 1), check_every))

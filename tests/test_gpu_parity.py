@@ -15,6 +15,7 @@ import torch
 import oracle as O
 import oracle.pipeline as OPL
 from conftest import ROOT, golden, golden_json
+from griddata_ref import _gradient_system, _interp_k_sweeps, _lattice, _scale_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -1108,12 +1109,6 @@ def test_match_legendre_multi_nan_and_nonsquare(gpu):
 
 # ----------------------------------------------------------------------------- griddata (f1)
 
-def _scale_tol(ref):
-    """1e-6 of the map's range, or 64 ulp of its largest magnitude (the 65x65 Wave2 carries a
-    ~1e7 nm offset, so rounding alone is ~1e-8 there)."""
-    return max(1e-6 * (np.nanmax(ref) - np.nanmin(ref)), 64 * np.spacing(np.nanmax(np.abs(ref))))
-
-
 def test_griddata_cubic_vs_reference(gpu):
     """The driver's griddata(cubic) of Wave2 on its 65x65 detector hits (the reference's output):
     same NaN mask (outside the hull), values to rounding."""
@@ -1125,15 +1120,6 @@ def test_griddata_cubic_vs_reference(gpu):
     ref = g["griddata_wave2"]
     assert np.array_equal(np.isnan(got), np.isnan(ref))
     assert np.nanmax(np.abs(got - ref)) <= _scale_tol(ref)
-
-
-def _lattice(nv, nh, seed):
-    u, v = np.meshgrid(np.linspace(-1, 1, nh), np.linspace(-1, 1, nv))
-    X = u * 1e-4 + 3e-6 * v ** 2 - 2e-6 * u * v + 1e-6 * v ** 3
-    Y = v * 1.3e-4 + 4e-6 * u ** 2 + 1e-6 * u ** 3
-    rng = np.random.default_rng(seed)
-    F = 0.3 * u ** 2 - 0.2 * u * v + 0.1 * np.sin(3 * v) + 1e-3 * rng.standard_normal(u.shape)
-    return X, Y, F
 
 
 @pytest.mark.parametrize("nv,nh", [(97, 113), (280, 300)])
@@ -1301,22 +1287,6 @@ def test_griddata_flagged_triangulation_stays_refused(gpu):
             cg2.interp_cone(F.ravel(), gx, gy)
 
 
-def _interp_k_sweeps(cg, vals, gx, gy, K):
-    """akb_gd_eval_f64 on the global Chebyshev iteration's gradients after exactly K sweeps."""
-    from akbraytracing_amd import _lib
-    from akbraytracing_amd import device as D
-    f = vals if isinstance(vals, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(vals))
-    f = f.to(cg.dev).reshape(-1, cg.nv * cg.nh).contiguous()
-    grad = cg.gradients(f, maxiter=K, check_every=K, adaptive=False, tol=0.0)
-    gxt, gyt = torch.from_numpy(gx).to(cg.dev), torch.from_numpy(gy).to(cg.dev)
-    mx, my, nv = gx.size, gy.size, int(f.shape[0])
-    owner = torch.empty(mx * my, dtype=torch.int32, device=cg.dev)
-    out = torch.empty((nv, my, mx), dtype=torch.float64, device=cg.dev)
-    _lib.check(_lib.lib().akb_gd_eval_f64(*cg._tri_args(), D.ptr(gxt), mx, D.ptr(gyt), my, D.ptr(f), D.ptr(grad), nv,
-                                          D.ptr(owner), D.ptr(out), D.stream_handle()))
-    return out.cpu().numpy()
-
-
 @pytest.mark.parametrize("nv,nh,m,nvals", [(97, 113, 40, 1), (280, 300, 128, 2), (300, 280, 57, 1), (70, 530, 90, 3)])
 def test_gradient_cone_equals_global_sweeps(gpu, nv, nh, m, nvals):
     """The cone solve (a patch per interior target cell, the boundary band with its pocket chords
@@ -1436,42 +1406,6 @@ def test_griddata_batched_values_and_errors(gpu):
     Xf[:, 25:] = 2 * X[:, 25].reshape(-1, 1) - X[:, 25:]   # fold the lattice back on itself
     with pytest.raises(_lib.AKBError):
         CubicGrid(Xf.ravel(), Y.ravel(), 40, 50)
-
-
-def _gradient_system(cg, f):
-    """scipy's gradient problem on cg's triangulation in numpy: per vertex the local solve's
-    Q = 4 sum r^-3 e e^T and s = sum (6 (f_i - f_j) + 2 e.g_j) r^-3 e over its edges (lattice edges by
-    the cell diagonals, a ring vertex's pocket chords from xptr / xidx) as the sparse fixed-point
-    problem g = c + J g (_interpnd.pyx's estimate_gradients_2d_global). Returns (J, c)."""
-    import scipy.sparse as sp
-    nv, nh = cg.nv, cg.nh
-    x, y = cg.x.cpu().numpy(), cg.y.cpu().numpy()
-    d = cg.diag.cpu().numpy().reshape(nv - 1, nh - 1).astype(bool)
-    idx = np.arange(nv * nh).reshape(nv, nh)
-    E = [(idx[:, :-1].ravel(), idx[:, 1:].ravel()), (idx[:-1, :].ravel(), idx[1:, :].ravel()),
-         (idx[:-1, :-1][~d], idx[1:, 1:][~d]), (idx[:-1, 1:][d], idx[1:, :-1][d])]
-    I = np.concatenate([e[0] for e in E])
-    J = np.concatenate([e[1] for e in E])
-    I, J = np.concatenate([I, J]), np.concatenate([J, I])
-    xptr, xidx = cg.xptr.cpu().numpy(), cg.xidx.cpu().numpy()
-    ring = np.concatenate([idx[0, :-1], idx[:-1, -1], idx[-1, :0:-1], idx[:0:-1, 0]])
-    ci = np.repeat(ring, np.diff(xptr))
-    I, J = np.concatenate([I, ci]), np.concatenate([J, xidx[:xptr[-1]]])
-    ex, ey = x[J] - x[I], y[J] - y[I]
-    r3 = (ex * ex + ey * ey) ** -1.5
-    n = nv * nh
-    q = [4 * np.bincount(I, w, n) for w in (ex * ex * r3, ex * ey * r3, ey * ey * r3)]
-    Qi = np.linalg.inv(np.stack([np.stack([q[0], q[1]], -1), np.stack([q[1], q[2]], -1)], -2))
-    w6 = 6 * (f[I] - f[J])
-    s0 = np.stack([np.bincount(I, w6 * ex * r3, n), np.bincount(I, w6 * ey * r3, n)], 1)
-    c = -np.einsum("nij,nj->ni", Qi, s0).ravel()
-    rows, cols, vals = [], [], []
-    for (a_, b_, w) in ((0, 0, ex * ex), (0, 1, ex * ey), (1, 0, ex * ey), (1, 1, ey * ey)):
-        rows.append(2 * I + a_)
-        cols.append(2 * J + b_)
-        vals.append(2 * w * r3)
-    A = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(2 * n, 2 * n))
-    return -(sp.block_diag(list(Qi), format="csr") @ A), c
 
 
 @pytest.mark.parametrize("nv,nh", [(97, 113), (300, 280), (33, 257)])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, golden_json
+from griddata_ref import _cell_tris_np, _pockets, _ring_np  # noqa: F401
 
 
 def test_library_exports_every_header_symbol():
@@ -266,45 +267,6 @@ def test_dropin_psf_module_exports():
 
 
 # ----------------------------------------------------------------------------- griddata triangulation
-
-def _cell_tris_np(X, Y):
-    """Cell split by the in-circle test (the rule the device cell pass applies), as vertex triples."""
-    nv, nh = X.shape
-    x0, y0 = X[:-1, :-1], Y[:-1, :-1]
-    bx, by = X[:-1, 1:] - x0, Y[:-1, 1:] - y0
-    cx, cy = X[1:, 1:] - x0, Y[1:, 1:] - y0
-    dx, dy = X[1:, :-1] - x0, Y[1:, :-1] - y0
-    adx, ady, bdx, bdy, cdx, cdy = -dx, -dy, bx - dx, by - dy, cx - dx, cy - dy
-    A, B, C = adx * adx + ady * ady, bdx * bdx + bdy * bdy, cdx * cdx + cdy * cdy
-    det = adx * (bdy * C - B * cdy) - ady * (bdx * C - B * cdx) + A * (bdx * cdy - bdy * cdx)
-    o = bx * cy - by * cx
-    diag = np.where(o > 0, det, -det) > 0
-    iv, ih = np.meshgrid(np.arange(nv - 1), np.arange(nh - 1), indexing="ij")
-    p00 = iv * nh + ih
-    p01, p10, p11 = p00 + 1, p00 + nh, p00 + nh + 1
-    t0 = np.where(diag[..., None], np.stack([p00, p01, p10], -1), np.stack([p00, p01, p11], -1))
-    t1 = np.where(diag[..., None], np.stack([p01, p11, p10], -1), np.stack([p00, p11, p10], -1))
-    return np.concatenate([t0.reshape(-1, 3), t1.reshape(-1, 3)])
-
-
-def _ring_np(nv, nh):
-    return np.array([ih for ih in range(nh - 1)] + [iv * nh + nh - 1 for iv in range(nv - 1)] +
-                    [(nv - 1) * nh + ih for ih in range(nh - 1, 0, -1)] + [iv * nh for iv in range(nv - 1, 0, -1)])
-
-
-def _pockets(X, Y):
-    from akbraytracing_amd import _lib
-    L = _lib.lib()
-    nv, nh = X.shape
-    r = _ring_np(nv, nh)
-    rx, ry = np.ascontiguousarray(X.ravel()[r]), np.ascontiguousarray(Y.ravel()[r])
-    cap = len(r)
-    tri, nbr = np.zeros((cap, 3), np.int32), np.zeros((cap, 3), np.int32)
-    edge, xptr, xidx, n = np.zeros(cap, np.int32), np.zeros(cap + 1, np.int32), np.zeros(6 * cap, np.int32), np.zeros(1, np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    _lib.check(L.akb_gd_pockets(p(rx), p(ry), nv, nh, cap, p(n), p(tri), p(nbr), p(edge), p(xptr), p(xidx)))
-    return tri[:n[0]], nbr[:n[0]], edge, xptr, xidx[:xptr[-1]]
-
 
 def _grids():
     from conftest import golden
